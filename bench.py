@@ -13,8 +13,8 @@ driver does (ShardedBatchLoader + gather_shards):
     -> zero-shot logits of the gathered rows (x @ visual.proj -> normalise
        -> 100 * f @ text_weights -> top-1; methods/ProLIP.py:288-293).
 --scaling strong (default): global batch 256 split 256/N per GPU
-(256/128/64/32 images per rank at N = 1/2/4/8); at N > 1 the line also carries
-the weak-scaling figure (256 images per GPU) timed in the same run.
+(256/128/64/32 images per rank at N = 1/2/4/8); with --full at N > 1 the line
+also carries the weak-scaling figure (256 images per GPU) timed in the same run.
 --scaling weak: 256 images per GPU, global batch 256 N.
 `value` = global images per step * K / max-over-ranks wall time of the K steps.
 
@@ -22,7 +22,19 @@ the weak-scaling figure (256 images per GPU) timed in the same run.
 spawned before anything touches the GPU); under torchrun (WORLD_SIZE set) it
 is one of the ranks. n_gpus is the world size RCCL actually formed.
 
-Also reported (rank 0): the dominant kernel's roofline (MLP c_fc GEMM:
+A plain run does what `value` needs and no more: it loads the model, warms up,
+times the K steps (the clock probe rides on the timed stream) and prints the
+line; the fields below that it did not measure are null. --dump-outputs DIR
+also writes what the last timed step returned (DIR/logits.npy, DIR/top1.npy,
+float32), so that two builds can be compared output for output: the inputs
+are seeded and identical from run to run.
+
+--full adds, as runs of their own beside the timed steps: at N > 1 the guard
+that the gathered rows equal the single-GPU encode, and the weak-scaling
+figure; a longer clock window when the timed region is too short for the
+probe; the --ab-* diagnostics; and what follows.
+
+Also reported with --full (rank 0): the dominant kernel's roofline (MLP c_fc GEMM:
 algorithmic FLOPs / its average launch time from HIP events of one profiled
 step, which runs the batch unsplit on one stream; traffic from the committed
 PMC profile of that same kernel and launch shape, else null), the whole-path
@@ -31,7 +43,8 @@ restatement of clip/model.py, oracle/clip_oracle.py, bit-exact with the
 reference on the same machine) timed on this host on a bounded sample.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong]
-                    [--model ViT-L/14] [--batch 256] [--ab-splits] [--ab-fold]
+                    [--model ViT-L/14] [--batch 256] [--dump-outputs DIR]
+                    [--full [--ab-splits] [--ab-fold]]
 """
 import argparse
 import json
@@ -61,6 +74,12 @@ def parse(argv=None):
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--scaling", default="strong", choices=["weak", "strong"])
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beside the headline figure: "
+                         "the N > 1 gather guard and weak-scaling figure, the profiled step "
+                         "(roofline, per-kernel table), the CPU baseline and the --ab-* diagnostics")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32)")
     ap.add_argument("--rehearse-gloo", action="store_true",
                     help="one-GPU rehearsal of the N-rank logic: gloo collectives, every rank on "
                          "cuda:(LOCAL_RANK mod devices); the line is marked, its value is not a "
@@ -72,9 +91,9 @@ def parse(argv=None):
                     help="images per GPU (weak) or global images (strong) per step")
     ap.add_argument("--dtype", default="fp16", choices=["fp16", "bf16", "mxfp8"])
     ap.add_argument("--classes", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-profile", action="store_true")
+    ap.add_argument("--no-profile", action="store_true", help="--full: skip the profiled step")
     ap.add_argument("--splits", type=int, default=2, help="encode_image batch split over streams")
     ap.add_argument("--ab-splits", action="store_true", help="also time splits=1 vs 2 (diagnostic)")
     ap.add_argument("--ab-gemm", default="",
@@ -86,7 +105,12 @@ def parse(argv=None):
     ap.add_argument("--ab-options", default="",
                     help="diagnostic: also time a second model with these options "
                          "('name=0|1,...', e.g. 'resid_f32=1') interleaved in this process")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full and (args.ab_splits or args.ab_gemm or args.ab_fold or args.ab_options):
+        ap.error("the --ab-* diagnostics are runs of their own: pass --full with them")
+    return args
 
 
 # ------------------------------------------------------------------ launcher --
@@ -187,6 +211,27 @@ def attach_traffic(model_name, dtype, epi, M):
     return t.get("hbm_bytes_per_launch"), t.get("source")
 
 
+# ----------------------------------------------------------------- outputs --
+
+DUMP_BYTES = 64 << 20     # all arrays of one dump together
+
+
+def dump_outputs(path, outputs):
+    """Write each output of the timed step as path/<name>.npy in float32. An array
+    over its share of DUMP_BYTES is cut to a fixed (seeded) sorted sample of its
+    rows, the same rows on every run."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // max(len(outputs), 1)
+    for name, t in outputs.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > share:
+            keep = max(1, share // max(a[0].nbytes, 1))
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))
+            a = a[rows]
+        np.save(os.path.join(path, f"{name}.npy"), a)
+
+
 # --------------------------------------------------------------------- rank --
 
 def _load_miclip(name, dev, dtype, options=None):
@@ -256,6 +301,7 @@ def run(args, backend="nccl", load_model=None):
     import torch.distributed as dist
 
     rehearse = bool(getattr(args, "rehearse_gloo", False))
+    full = bool(getattr(args, "full", False))
     on_gpu = backend == "nccl" or rehearse
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -352,8 +398,9 @@ def run(args, backend="nccl", load_model=None):
         t0 = time.perf_counter()
         if clock is not None:
             clock.mark(0)
+        out = None
         for _ in range(steps):
-            fn()
+            out = fn()
         if clock is not None:
             clock.mark(1)
         sync()
@@ -363,7 +410,7 @@ def run(args, backend="nccl", load_model=None):
         dt_t = torch.tensor([dt], device="cpu" if rehearse else dev, dtype=torch.float64)
         if world > 1:
             dist.all_reduce(dt_t, op=dist.ReduceOp.MAX)
-        return float(dt_t.item())
+        return float(dt_t.item()), out     # the time, and what the last step returned
 
     def clock_window(fn, per_step_s):
         """A clock reading over >= ClockProbe.MIN_WINDOW_S of back-to-back steps
@@ -374,9 +421,9 @@ def run(args, backend="nccl", load_model=None):
         timed(fn, n, c)
         return c, n
 
-    # correctness guard on the timed path: the first 4 rows of every rank's slice,
-    # gathered, are the single-GPU encode of those images in global order
-    if world > 1:
+    # correctness guard on the timed path (--full): the first 4 rows of every rank's
+    # slice, gathered, are the single-GPU encode of those images in global order
+    if full and world > 1:
         k = min(4, hi - lo)
         firsts = [shard_range(n_global, r, world) for r in range(world)]
         chk = gather_shards(model.encode_image(imgs[:k], normalize=True) if k else None, width=W,
@@ -389,17 +436,22 @@ def run(args, backend="nccl", load_model=None):
     for _ in range(args.warmup):
         step()
     clock = ClockProbe(dev) if on_gpu else None
-    dt = timed(step, args.steps, clock)
+    dt, (logits, top1) = timed(step, args.steps, clock)
     value = n_global * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed step receives: the zero-shot logits of the
+        # gathered rows [n_global, classes] and their top-1 class
+        dump_outputs(args.dump_outputs, {"logits": logits, "top1": top1})
+    del logits, top1
     clock_steps = args.steps
     if clock is not None and dt < ClockProbe.MIN_WINDOW_S:
-        # the timed region is too short for the probe: read the clock over a
-        # longer run of the same step right after it
-        clock, clock_steps = clock_window(step, dt / args.steps)
+        # the timed region is too short for the probe: with --full read the clock
+        # over a longer run of the same step right after it, else report none
+        clock, clock_steps = clock_window(step, dt / args.steps) if full else (None, 0)
     clock_ghz, clock_xcd, clock_rej = clock.ghz() if clock is not None else (None, {}, {})
 
     weak = None
-    if args.scaling == "strong" and world > 1 and not args.no_weak:
+    if full and args.scaling == "strong" and world > 1 and not args.no_weak:
         # the weak-scaling figure of the same run: --batch (256) images per GPU
         n_w = args.batch * world
         wlo, whi = shard_range(n_w, rank, world)
@@ -409,7 +461,7 @@ def run(args, backend="nccl", load_model=None):
         for _ in range(max(args.warmup, 1)):
             wstep()
         wsteps = max(3, args.steps * (hi - lo) // 256)
-        wdt = timed(wstep, wsteps)
+        wdt, _ = timed(wstep, wsteps)
         weak = {"value": round(n_w * wsteps / wdt, 2), "images_per_gpu": whi - wlo,
                 "global_batch": n_w, "steps": wsteps, "ms_per_step": round(wdt / wsteps * 1e3, 3),
                 "path_mfma_frac": None}
@@ -419,17 +471,17 @@ def run(args, backend="nccl", load_model=None):
     gf_exec = executed_gflop_per_image(cfg, cls_last=cls_last)
 
     ab = None
-    if args.ab_splits:
+    if full and args.ab_splits:
         ab = {}
         for sp in (1, 2, 3, 1, 2, 3):
             model.set_splits(sp)
             eff = model.image_splits(max(hi - lo, 1))   # the part count actually run
             step()
             ab.setdefault(f"splits{sp}" + (f"_ran{eff}" if eff != sp else ""), []).append(
-                round(n_global * args.steps / timed(step, args.steps), 1))
+                round(n_global * args.steps / timed(step, args.steps)[0], 1))
         model.set_splits(args.splits)
     abg = None
-    if args.ab_gemm:
+    if full and args.ab_gemm:
         abg = {}
         pairs = [tuple(int(x) for x in p.split(":")) for p in args.ab_gemm.split(",")]
         for _ in range(3):
@@ -438,12 +490,12 @@ def run(args, backend="nccl", load_model=None):
                     model.set_gemm_variant(which, v)
                 step()
                 abg.setdefault(":".join(map(str, pv)), []).append(
-                    round(n_global * args.steps / timed(step, args.steps), 1))
+                    round(n_global * args.steps / timed(step, args.steps)[0], 1))
         for which in range(3):
             model.set_gemm_variant(which, 0)
         abg = {k: dict(runs=v, median=statistics.median(v)) for k, v in abg.items()}
     abf = None
-    if args.ab_fold or args.ab_options:
+    if full and (args.ab_fold or args.ab_options):
         alt = ({"ln_fold": False} if args.ab_fold else
                {k: bool(int(v)) for k, v in (p.split("=") for p in args.ab_options.split(","))})
         m0 = load_model(args.model, dev, args.dtype, options=alt)
@@ -456,8 +508,8 @@ def run(args, backend="nccl", load_model=None):
         abf = {"fold": [], "nofold": [], "fold_flags": model.numerics(), "nofold_flags": m0.numerics(),
                "alt_options": alt}
         for _ in range(3):
-            abf["fold"].append(round(n_global * args.steps / timed(step, args.steps), 1))
-            abf["nofold"].append(round(n_global * args.steps / timed(step0, args.steps), 1))
+            abf["fold"].append(round(n_global * args.steps / timed(step, args.steps)[0], 1))
+            abf["nofold"].append(round(n_global * args.steps / timed(step0, args.steps)[0], 1))
         abf["fold_median"] = statistics.median(abf["fold"])
         abf["nofold_median"] = statistics.median(abf["nofold"])
         del m0, step0
@@ -466,7 +518,7 @@ def run(args, backend="nccl", load_model=None):
 
     roofline, kernels = None, None
     prof = None
-    if not args.no_profile:
+    if full and not args.no_profile:
         # every rank runs the profiled step (it contains the all-gather); profiling
         # runs each rank's batch unsplit on one stream, so a GEMM launch has M = b*N
         model.set_profiling(True)
@@ -516,7 +568,7 @@ def run(args, backend="nccl", load_model=None):
                                      if clock_ghz else None)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(model, cfg, budget_s=args.cpu_seconds)
 
     if rank == 0:

@@ -14,7 +14,7 @@ if [ $# -gt 0 ]; then
 fi
 for r in $(seq 1 ${R:-3}); do
   for L in build/base/libmiclip_base.so aihab-clip_amd/miclip/libmiclip.so; do
-    MICLIP_LIB=$L timeout -k 10 200 python bench.py --steps 10 --warmup 3 --no-cpu-baseline ${BENCH_ARGS:-} > $O/b_${r}_$(basename $L .so).json 2> $O/b_${r}_$(basename $L .so).err || { echo "bench failed ($L)"; exit 1; }
+    MICLIP_LIB=$L timeout -k 10 200 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline ${BENCH_ARGS:-} > $O/b_${r}_$(basename $L .so).json 2> $O/b_${r}_$(basename $L .so).err || { echo "bench failed ($L)"; exit 1; }
     python3 -c "
 import json,sys; d=json.loads(open('$O/b_${r}_$(basename $L .so).json').read().strip().splitlines()[-1])
 k=d.get('kernels',{})

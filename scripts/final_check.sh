@@ -9,5 +9,5 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout
   && tail -1 $O/pytest_gpu.log \
   && timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1 \
   && tail -1 $O/smoke.log \
-  && timeout -k 10 300 python bench.py > $O/bench.json 2> $O/bench.err \
+  && timeout -k 10 300 python bench.py --full > $O/bench.json 2> $O/bench.err \
   && python3 -c "import json; d=json.loads(open('$O/bench.json').read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], d['roofline']['frac'], d['path_mfma_frac'], d['clock_ghz'])"

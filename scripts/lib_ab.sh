@@ -22,7 +22,7 @@ done
 for r in $(seq 1 ${R:-3}); do
   for L in aihab-clip_amd/miclip/libmiclip.so $EXP; do
     n=$(basename $L .so)
-    MICLIP_LIB=$L timeout -k 10 200 python bench.py --steps 10 --warmup 3 --no-cpu-baseline ${BENCH_ARGS:-} > $O/b_${r}_$n.json 2> $O/b_${r}_$n.err || { echo "bench failed ($L)"; exit 1; }
+    MICLIP_LIB=$L timeout -k 10 200 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline ${BENCH_ARGS:-} > $O/b_${r}_$n.json 2> $O/b_${r}_$n.err || { echo "bench failed ($L)"; exit 1; }
     python3 -c "
 import json; d=json.loads(open('$O/b_${r}_$n.json').read().strip().splitlines()[-1]); k=d.get('kernels',{})
 print('$n', d['value'], 'clk', d.get('clock_ghz'), ' '.join(f'{n}={v[\"ms\"]:.3f}' for n,v in k.items() if v['ms']>0.1))"

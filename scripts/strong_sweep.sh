@@ -11,7 +11,7 @@ O=gpurun_out/${OUT:-strong}
 mkdir -p $O
 for b in ${BATCHES:-256 128 64 32 16}; do
   s=$(( 2560 / b )); [ $s -lt 10 ] && s=10
-  ${LIB:+env MICLIP_LIB=$LIB} timeout -k 10 300 python bench.py --scaling strong --batch $b --steps $s --warmup 3 \
+  ${LIB:+env MICLIP_LIB=$LIB} timeout -k 10 300 python bench.py --full --scaling strong --batch $b --steps $s --warmup 3 \
       --no-cpu-baseline ${EXTRA:-} > $O/bs$b.json 2> $O/bs$b.err || { echo "bench bs=$b failed"; tail -5 $O/bs$b.err; exit 1; }
   python3 - "$O/bs$b.json" <<'EOF'
 import json, sys

@@ -68,7 +68,7 @@ def _stub_loader(name, dev, dtype, options=None):
 
 
 ARGV = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "4", "--model", "ViT-B/32",
-        "--classes", "5", "--no-profile", "--no-cpu-baseline"]
+        "--classes", "5", "--full", "--no-profile", "--no-cpu-baseline"]   # --full: guard + weak figure
 
 
 def _rank(rank, world, port, q, extra):
@@ -121,3 +121,39 @@ def test_bench_rank_logic_world1_host(monkeypatch):
     line = bench.run(bench.parse(argv), backend="gloo", load_model=_stub_loader)
     assert line["n_gpus"] == 1 and line["config"]["global_batch"] == 4
     assert line["gflop_per_image_executed"] < line["gflop_per_image"]
+
+
+def test_bench_plain_run_dumps_last_step(monkeypatch, tmp_path):
+    """A plain run (no --full) times the steps and nothing else, and --dump-outputs
+    writes what the last timed step returned: float32 arrays (the logits and their
+    top-1 class), the same from run to run since the inputs are seeded."""
+    import numpy as np
+    import bench
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
+        monkeypatch.delenv(k, raising=False)
+    argv = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "4", "--model", "ViT-B/32",
+            "--classes", "5"]
+    calls = []
+
+    def loader(*a, **kw):
+        calls.append(StubModel())
+        return calls[-1]
+    dumps = []
+    for d in ("a", "b"):
+        line = bench.run(bench.parse(argv + ["--dump-outputs", str(tmp_path / d)]), backend="gloo",
+                         load_model=loader)
+        assert line["steps"] == 2 and line["value"] > 0 and line["ms_per_step"] > 0
+        assert line["value"] == pytest.approx(4 * 2 / (line["ms_per_step"] * 2 / 1e3), rel=1e-2)
+        assert line["roofline"] is None and line["cpu_baseline"] is None and line["kernels"] is None
+        assert calls[-1].calls == 3                      # warmup + steps, nothing beside them
+        assert sorted(os.listdir(tmp_path / d)) == ["logits.npy", "top1.npy"]
+        dumps.append({n: np.load(tmp_path / d / f"{n}.npy") for n in ("logits", "top1")})
+    a, b = dumps
+    assert a["logits"].dtype == np.float32 and a["logits"].shape == (4, 5)
+    assert a["top1"].dtype == np.float32 and a["top1"].shape == (4, 1)
+    assert np.array_equal(a["logits"], b["logits"]) and np.array_equal(a["top1"], b["top1"])
+    assert np.array_equal(a["top1"][:, 0], a["logits"].argmax(axis=1))
+    with pytest.raises(SystemExit):
+        bench.parse(argv + ["--ab-splits"])              # diagnostics are --full runs
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])

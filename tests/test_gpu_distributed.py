@@ -86,7 +86,7 @@ def test_bench_two_rank_rehearsal():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(root, "bench.py"), "--gpus", "2", "--rehearse-gloo", "--model", "ViT-B/32",
-           "--steps", "3", "--warmup", "1", "--no-cpu-baseline"]
+           "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=280, cwd=root)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -11,7 +11,9 @@ from miclip.feature_cache import (_canonical_backbone_name, _embedding_cache_dir
                                   _feature_cache_dir, _feature_cache_exists, shard_range)
 from miclip.weights import param_specs
 
-REF_BPE = "/root/reference/clip/bpe_simple_vocab_16e6.txt.gz"
+# the ranked merges the tokenizer reads (header line + the first 49152 - 256 - 2
+# merges of the CLIP table bpe_simple_vocab_16e6.txt.gz), stored as a fixture
+BPE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "bpe_merges_49152.txt.gz")
 
 
 # build_model's shape inference (clip/model.py:396-419) only covers OpenAI CLIP
@@ -69,11 +71,10 @@ def test_shard_range_partitions(n, world):
     assert max(sizes) - min(sizes) <= 1
 
 
-@pytest.mark.skipif(not os.path.isfile(REF_BPE), reason="BPE vocabulary not available")
 def test_tokenizer_matches_reference_tokens(golden, monkeypatch):
-    monkeypatch.setenv("MICLIP_BPE_PATH", REF_BPE)
+    monkeypatch.setenv("MICLIP_BPE_PATH", BPE)
     import miclip.tokenizer as tk
-    tk._tok = None
+    monkeypatch.setattr(tk, "_tok", None)
     for tag in ("vitb32", "vitl14"):
         g = golden(tag)
         got = miclip.tokenize(g["meta"]["prompts"])

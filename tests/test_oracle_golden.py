@@ -9,11 +9,11 @@ Bit-exactness is a same-machine property: torch's fp32 CPU GEMM kernels pick
 their blocking (and so their summation order) by CPU model and ISA, so the
 fixtures (made on the round-1 Intel host) and an AMD EPYC host differ by
 ~2e-6 at |x| ~ 4. Against the committed fixtures the bound is therefore
-CPU_TOL (fp32 reassociation, 5e-6 relative); when the reference is present
-(the build container), test_oracle_bit_exact_vs_reference_here re-runs the
-reference on THIS machine and requires the oracle to match it bit for bit.
+CPU_TOL (fp32 reassociation, 5e-6 relative). The same-machine bit-for-bit
+comparison needs the reference's own clip/model.py, which is not part of this
+repository: oracle/make_golden.py, which regenerates the fixtures from a
+reference checkout, is where the two run side by side.
 """
-import os
 import numpy as np
 import pytest
 import torch
@@ -23,7 +23,6 @@ from miclip.weights import generate_state_dict, synthetic_images, checksum
 from oracle import clip_oracle
 
 CPU_TOL = 2e-5     # max |d| vs fixtures made on another CPU (see module docstring)
-REF = os.environ.get("MICLIP_REFERENCE", "/root/reference")
 
 TAGS = {"vitb32": "ViT-B/32", "vitb16": "ViT-B/16", "vitl14": "ViT-L/14",
         "vitl14_336": "ViT-L/14@336px", "vith14": "ViT-H-14"}
@@ -106,27 +105,3 @@ def test_golden_tokens_well_formed(golden):
         eot = tok.argmax(axis=1)
         assert (tok[np.arange(len(tok)), eot] == 49407).all()
         assert all((row[e + 1:] == 0).all() for row, e in zip(tok, eot))
-
-
-@pytest.mark.skipif(not os.path.isfile(os.path.join(REF, "clip", "model.py")),
-                    reason="reference checkout absent (only the build container has it)")
-def test_oracle_bit_exact_vs_reference_here(golden):
-    """Same machine, same torch: the oracle equals the reference clip/model.py
-    (build_model + .float(), clip/clip.py:133-137) bit for bit -- image tower,
-    text tuple and the clip_classifier / ProLIP head (oracle/make_golden.py)."""
-    import sys
-    sys.dont_write_bytecode = True
-    from oracle import make_golden
-    refmodel = make_golden._load("_ref_clip_model", os.path.join(REF, "clip", "model.py"))
-    cfg = MODEL_CONFIGS["ViT-B/32"]
-    sd = generate_state_dict(cfg, seed=0)
-    model = make_golden.reference_model(refmodel, sd, cfg)
-    imgs = synthetic_images(3, cfg.image_resolution, seed=0)
-    tokens = golden("vitb32")["tokens"][:4]
-    torch.set_num_threads(8)
-    with torch.no_grad():
-        ref_img = model.encode_image(torch.from_numpy(imgs))
-        ref_b, ref_p = model.encode_text(torch.from_numpy(tokens).long())
-    assert torch.equal(clip_oracle.encode_image(sd, cfg, imgs), ref_img)
-    ob, op = clip_oracle.encode_text(sd, cfg, tokens)
-    assert torch.equal(ob, ref_b) and torch.equal(op, ref_p)
