@@ -1022,6 +1022,30 @@ int miclip_proto_scores(const float* x, const float* protos, const int32_t* owne
   return 0;
 }
 
+int miclip_prolip_grad(const void* x, int32_t x_dtype, const int64_t* labels, int32_t n, int32_t D,
+                       int32_t E, int32_t C, const float* text_weights, const float* P,
+                       int32_t G, float scale, float* dZ, float* partials, void* stream) {
+  if (!x || !labels || !text_weights || !P || !dZ || !partials)
+    return fail(MICLIP_EINVAL, "null argument");
+  MICLIP_HIP(prolip_grad(x_dtype, x, labels, text_weights, P, dZ, partials, n, D, E, C, G, scale,
+                         (hipStream_t)stream));
+  return 0;
+}
+
+int miclip_prolip_adam(const void* x, int32_t x_dtype, const float* dZ, int32_t n, int32_t D,
+                       int32_t E, int32_t G, const float* P0, float* P, float* m, float* v,
+                       const float* lr, const float* lambda, float lr_factor, float lambda_div,
+                       int32_t step, float eps, const float* grad_partials, float* mse_partials,
+                       float* history, void* stream) {
+  if (!x || !dZ || !P0 || !P || !m || !v || !lr || !lambda || !grad_partials || !mse_partials ||
+      !history)
+    return fail(MICLIP_EINVAL, "null argument");
+  MICLIP_HIP(prolip_adam(x_dtype, x, dZ, P0, P, m, v, lr, lambda, grad_partials, mse_partials,
+                         history, n, D, E, G, lr_factor, lambda_div, step, eps,
+                         (hipStream_t)stream));
+  return 0;
+}
+
 int miclip_set_profiling(miclip_model* m, int enable) {
   if (!m) return fail(MICLIP_EINVAL, "null model");
   m->profiling = enable != 0;

@@ -160,6 +160,28 @@ hipError_t proto_scores(const float* x, const float* protos, const int32_t* owne
                         int P, int D, float* own_best, int32_t* own_arg, float* other_best,
                         hipStream_t s);
 
+// ---- ProLIP projector training on cached features (prolip.hip), fp32 ----
+// One optimiser step of G configurations that share x [n, D] (x_dtype kIn32 / kF16 /
+// kBF16, 16-B aligned), labels [n] in [0, C), W [E, C] and P0 [D, E] and differ in
+// P / m / v [G, D, E], lr [G], lam [G]. D, E % 16 == 0, 16 <= D <= 1280,
+// 16 <= E <= 1024, 1 <= C <= 1024, G <= 65535.
+// prolip_grad: dZ [G, n, E] = d(mean CE of scale * normalize(x P_g) W) / d(x P_g);
+// part [G, ceil(n/16), 2] = per 16-row tile {sum of CE, rows with argmax == label}.
+hipError_t prolip_grad(int x_dtype, const void* x, const int64_t* labels, const float* W,
+                       const float* P, float* dZ, float* part, int n, int D, int E, int C, int G,
+                       float scale, hipStream_t s);
+// prolip_adam: dP = x^T dZ_g + 2 (lam_g / lambda_div) (P_g - P0), then torch.optim.Adam's
+// step `step` (1-based; betas 0.9 / 0.999, no weight decay) with lr_g * lr_factor on
+// P_g, m_g, v_g; mse_part [G, prolip_adam_tiles(D, E)] = per-tile sum((P_g - P0)^2) before
+// the update; history [G, 3] = {mean CE, that MSE, correct count} folded from
+// grad_part (prolip_grad's part) and mse_part in a fixed order.
+int prolip_adam_tiles(int D, int E);
+hipError_t prolip_adam(int x_dtype, const void* x, const float* dZ, const float* P0, float* P,
+                       float* m, float* v, const float* lr, const float* lam,
+                       const float* grad_part, float* mse_part, float* history, int n, int D,
+                       int E, int G, float lr_factor, float lambda_div, int step, float eps,
+                       hipStream_t s);
+
 // ---- on-device CLIP preprocessing (bicubic resize + center crop + normalise) ----
 // PreCache: geometry-table cache + image-array buffers, one per model handle.
 // descs: HOST array of B descriptors (validated, copied stream-ordered);

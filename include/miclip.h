@@ -216,6 +216,44 @@ int miclip_proto_scores(const float* x, const float* protos, const int32_t* owne
                         int32_t P, int32_t D, float* own_best, int32_t* own_arg,
                         float* other_best, void* stream);
 
+/* ---- ProLIP projector training on the pre-projection feature cache, fp32 ----
+ * One optimiser step of G configurations (the (lr, lambda) grid of search_lr,
+ * or G = 1) per pair of calls. They share x [n, D] (x_dtype MICLIP_F32,
+ * MICLIP_FP16 or MICLIP_BF16, widened in the load; 16-byte aligned), labels
+ * [n] int64 in [0, C), text_weights [E, C] and P0 [D, E], and differ in
+ * P / m / v [G, D, E], lr [G] and lambda [G]. D % 16 == 0, E % 16 == 0,
+ * 16 <= D <= 1280, 16 <= E <= 1024, 1 <= C <= 1024, n >= 1, 1 <= G <= 65535;
+ * anything else is MICLIP_EINVAL before any launch. All pointers are device
+ * memory owned by the caller; both calls are stream-ordered, never synchronise
+ * and never allocate. Results are deterministic and a configuration's result
+ * does not depend on G or on its index.
+ *
+ * miclip_prolip_grad replaces the forward and the autograd backward of
+ * methods/ProLIP.py:232-234, 244, 248 (:202-204, 214, 218 chunked; :337-340,
+ * 351 in search_init_hp): logits = scale * normalize(x @ P_g) @ text_weights,
+ * loss1 = cross_entropy(logits, labels), and dZ [G, n, E] = d loss1 / d(x @
+ * P_g). partials [G, ceil(n / 16), 2] receives per 16-row tile {sum of the
+ * rows' cross-entropy, number of rows with argmax(logits) == label}. */
+int miclip_prolip_grad(const void* x, int32_t x_dtype, const int64_t* labels, int32_t n, int32_t D,
+                       int32_t E, int32_t C, const float* text_weights, const float* P,
+                       int32_t G, float scale, float* dZ, float* partials, void* stream);
+/* miclip_prolip_adam replaces the rest of the step, methods/ProLIP.py:243-256
+ * (:213-226 chunked; :350-358) with the optimiser of :165-166 (:316-317):
+ * dP = x^T dZ_g + 2 (lambda_g / lambda_div) (P_g - P0), never written, then
+ * torch.optim.Adam's update (betas 0.9 / 0.999, eps, bias correction by the
+ * 1-based `step`, no weight decay) of P_g, m_g, v_g with the rate lr_g *
+ * lr_factor; lr_factor is CosineAnnealingLR's 0.5 (1 + cos(pi epoch / T)),
+ * lambda_div the chunk count of :193-195 (1 when not chunked).
+ * grad_partials: miclip_prolip_grad's partials of the same step; mse_partials:
+ * scratch [G, ceil(D / 32) * ceil(E / 32)]; history [G, 3] receives {loss1,
+ * loss2 = sum((P_g - P0)^2) before the update, correct count}: what the
+ * reference reads back with .item() at :248-252. */
+int miclip_prolip_adam(const void* x, int32_t x_dtype, const float* dZ, int32_t n, int32_t D,
+                       int32_t E, int32_t G, const float* P0, float* P, float* m, float* v,
+                       const float* lr, const float* lambda, float lr_factor, float lambda_div,
+                       int32_t step, float eps, const float* grad_partials, float* mse_partials,
+                       float* history, void* stream);
+
 /* Batch split of encode_image over the caller's stream and one handle-owned
  * stream (fork/join by events, so the call stays stream-ordered and
  * graph-capturable): 1 = off, 2..4 = that many parts (default 2; a part is
