@@ -89,6 +89,13 @@ def bar(e_ref, P0):
     return 4.0 * max(float(e_ref), 8.0 * EPS32 * float(np.abs(np.asarray(P0)).max()))
 
 
+def bar_on(e_ref, want):
+    """bar() with the 8 ulp floor taken on the compared quantity itself, for values
+    whose scale has nothing to do with the weights' (Adam's m and v: v is about 1e-6,
+    where 8 ulp of max|P0| would be about 6e-7 and allow an error as large as v)."""
+    return 4.0 * max(float(e_ref), 8.0 * EPS32 * float(np.abs(np.asarray(want)).max()))
+
+
 def case_inputs(gold, case):
     """(views [V][n, D] float32 arrays, labels [n], P0, W, lrs, lams, epochs, feat_batch_size)
     of golden case 'a' / 'b' / 'c' / 's' after the label filter."""
