@@ -1046,6 +1046,31 @@ int miclip_prolip_adam(const void* x, int32_t x_dtype, const float* dZ, int32_t 
   return 0;
 }
 
+int64_t miclip_eval_state_bytes(int32_t C, int32_t num_l2) {
+  return (int64_t)eval_state_bytes(C, num_l2);
+}
+
+int miclip_eval_reset(void* state, int32_t C, int32_t num_l2, void* stream) {
+  if (!state) return fail(MICLIP_EINVAL, "null argument");
+  MICLIP_HIP(eval_reset(state, C, num_l2, (hipStream_t)stream));
+  return 0;
+}
+
+int miclip_eval_batch(const void* feats, int32_t f_dtype, const float* text_weights,
+                      const int64_t* labels, int32_t B, int32_t E, int32_t C, float scale,
+                      const int32_t* l3_to_l2, int32_t num_l2, int32_t l2_mode, uint32_t flags,
+                      void* state, float* logits, float* row_loss, int32_t* row_pred,
+                      int32_t* row_top3, float* row_top3_prob, int32_t* l2_pred,
+                      int32_t* l2_top3, float* l2_logits, void* stream) {
+  if (flags & ~MICLIP_EVAL_LOGITS_IN) return fail(MICLIP_EINVAL, "unknown flag bits");
+  if (!labels || !state || !row_loss) return fail(MICLIP_EINVAL, "null argument");
+  MICLIP_HIP(eval_batch(f_dtype, feats, text_weights, labels, B, E, C, scale, l3_to_l2, num_l2,
+                        l2_mode, (flags & MICLIP_EVAL_LOGITS_IN) != 0, state, logits, row_loss,
+                        row_pred, row_top3, row_top3_prob, l2_pred, l2_top3, l2_logits,
+                        (hipStream_t)stream));
+  return 0;
+}
+
 int miclip_set_profiling(miclip_model* m, int enable) {
   if (!m) return fail(MICLIP_EINVAL, "null model");
   m->profiling = enable != 0;

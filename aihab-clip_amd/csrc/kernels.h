@@ -182,6 +182,31 @@ hipError_t prolip_adam(int x_dtype, const void* x, const float* dZ, const float*
                        int E, int G, float lr_factor, float lambda_div, int step, float eps,
                        hipStream_t s);
 
+// ---- validation metrics (evaluate.hip), fp32 ----
+// The caller-owned state block, as 8-byte words (include/miclip.h documents it):
+// word 0 the float64 sum of batch-mean losses, words 1..7 integer counters, then the
+// L3 confusion counts [C, C] and the L2 confusion counts [num_l2, num_l2].
+enum EvalWord {
+  kEvalLoss = 0, kEvalRows = 1, kEvalBatches = 2, kEvalTop1 = 3, kEvalTop3 = 4, kEvalL2Top1 = 5,
+  kEvalL2Top3 = 6, kEvalSkipped = 7, kEvalHeaderWords = 8
+};
+// l2_mode (MICLIP_EVAL_L2_* in include/miclip.h)
+enum EvalL2 { kEvalL2None = 0, kEvalL2Argmax = 1, kEvalL2Sum = 2, kEvalL2Mean = 3,
+              kEvalL2LogSumExp = 4 };
+size_t eval_state_bytes(int C, int num_l2);   // 0 for an unsupported (C, num_l2)
+hipError_t eval_reset(void* state, int C, int num_l2, hipStream_t s);
+// One batch: eval_rows_kernel (16 rows per workgroup) + eval_finalise_kernel. f [B, E]
+// (f_dtype kIn32 / kF16 / kBF16, 16-B aligned), tw [E, C], labels [B]; with logits_in
+// the logits [B, C] are read instead of computed (f, tw, E unused). l3_to_l2_host: HOST
+// int32 [C], required exactly when l2_mode != kEvalL2None, entries in [0, num_l2).
+// E % 16 == 0, 16 <= E <= 1024, 3 <= C <= 1024, 1 <= num_l2 <= C, B >= 1. row_loss [B]
+// is required; every other output may be null.
+hipError_t eval_batch(int f_dtype, const void* f, const float* tw, const int64_t* labels, int B,
+                      int E, int C, float scale, const int32_t* l3_to_l2_host, int num_l2,
+                      int l2_mode, bool logits_in, void* state, float* logits, float* row_loss,
+                      int32_t* row_pred, int32_t* row_top3, float* row_top3_prob, int32_t* l2_pred,
+                      int32_t* l2_top3, float* l2_logits, hipStream_t s);
+
 // ---- on-device CLIP preprocessing (bicubic resize + center crop + normalise) ----
 // PreCache: geometry-table cache + image-array buffers, one per model handle.
 // descs: HOST array of B descriptors (validated, copied stream-ordered);

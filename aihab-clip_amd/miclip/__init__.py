@@ -13,14 +13,20 @@ import warnings
 
 import torch
 
+from . import evaluation
 from .configs import (MODEL_CONFIGS, OPEN_CLIP_MODELS, CLIPConfig, available_models,
                       config_from_state_dict)
+from .evaluation import (ClassificationTracker, Evaluator, L2MetricsAccumulator,
+                         aggregate_logits_to_l2, evaluate_features, map_l3_targets_to_l2,
+                         run_validation)
 from .model import CLIP, build_model
 from .preprocess import Transform
 from .weights import generate_state_dict, synthetic_images
 
 __all__ = ["available_models", "load", "tokenize", "build_model", "CLIP", "CLIPConfig",
-           "MODEL_CONFIGS", "SeededWeightsWarning"]
+           "MODEL_CONFIGS", "SeededWeightsWarning", "evaluation", "run_validation",
+           "evaluate_features", "Evaluator", "L2MetricsAccumulator", "ClassificationTracker",
+           "aggregate_logits_to_l2", "map_l3_targets_to_l2"]
 
 
 class SeededWeightsWarning(UserWarning):

@@ -46,11 +46,19 @@ EXPORTS = (
     "miclip_op_layernorm", "miclip_op_attention", "miclip_op_attention_q0", "miclip_op_im2col", "miclip_preprocess",
     "miclip_row_norms", "miclip_class_centroids", "miclip_proto_scores",
     "miclip_prolip_grad", "miclip_prolip_adam",
+    "miclip_eval_state_bytes", "miclip_eval_reset", "miclip_eval_batch",
     "miclip_mx_scale_bytes", "miclip_op_quant_mx", "miclip_op_gemm_mx", "miclip_op_gemm_mx_v", "miclip_op_layernorm_mx",
 )
 
 MICLIP_PRE_F32 = 0
 MICLIP_PRE_U8 = 1
+# miclip_eval_batch l2_mode / flags (include/miclip.h MICLIP_EVAL_*)
+MICLIP_EVAL_L2_NONE = 0
+MICLIP_EVAL_L2_ARGMAX = 1
+MICLIP_EVAL_L2_SUM = 2
+MICLIP_EVAL_L2_MEAN = 3
+MICLIP_EVAL_L2_LOGSUMEXP = 4
+MICLIP_EVAL_LOGITS_IN = 1
 
 
 class MiclipConfig(ctypes.Structure):
@@ -143,6 +151,10 @@ def load_library(path: str = None):
                                ctypes.c_int),
         "miclip_prolip_adam": ([vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, f32, f32,
                                 i32, f32, vp, vp, vp, vp], ctypes.c_int),
+        "miclip_eval_state_bytes": ([i32, i32], i64),
+        "miclip_eval_reset": ([vp, i32, i32, vp], ctypes.c_int),
+        "miclip_eval_batch": ([vp, i32, vp, vp, i32, i32, i32, f32, vp, i32, i32, u32, vp, vp, vp,
+                               vp, vp, vp, vp, vp, vp, vp], ctypes.c_int),
     }
     # an explicitly declared A/B build of an older revision (MICLIP_LIB together with
     # MICLIP_AB_BUILD=1) may predate some op-level entry points: those stay unbound

@@ -254,6 +254,66 @@ int miclip_prolip_adam(const void* x, int32_t x_dtype, const float* dZ, int32_t 
                        int32_t step, float eps, const float* grad_partials, float* mse_partials,
                        float* history, void* stream);
 
+/* ---- validation metrics on features or logits, fp32 ----
+ * Replace the body of _run_validation's batch loop (methods/PEFT_openclip.py:
+ * 89-117) and the per-batch work of aihab_utils/evaluation.py (cls_acc top-1 /
+ * top-3, CrossEntropyLoss, the confusion-matrix / F1 updates, L2MetricsAccumulator
+ * .update :186-221, aggregate_logits_to_l2 :92-142, ClassificationTracker
+ * .top3_metrics :261-273). They need no model handle, are stream-ordered, never
+ * synchronise and never allocate.
+ *
+ * The state block is caller-owned device memory of miclip_eval_state_bytes(C,
+ * num_l2) bytes, 8-byte aligned, read back with one copy. As 8-byte words:
+ *   0                    float64  sum over batches of the batch-mean cross-entropy
+ *   1                    int64    rows counted
+ *   2                    int64    batches
+ *   3, 4                 int64    top-1 hits, top-3 hits
+ *   5, 6                 int64    L2 top-1 hits, L2 top-min(3, num_l2) hits
+ *   7                    int64    rows skipped (label outside [0, C), or NaN logits)
+ *   8 ..                 int64    L3 confusion counts [C, C], row = label, column =
+ *                                 prediction
+ *   8 + C*C ..           int64    L2 confusion counts [num_l2, num_l2]
+ * All integer words are exact and do not depend on the order of the batches.
+ * miclip_eval_state_bytes returns 0 unless 3 <= C <= 1024 and 1 <= num_l2 <= C
+ * (pass num_l2 = 1 when no L2 map is used). miclip_eval_reset zeroes the block. */
+int64_t miclip_eval_state_bytes(int32_t C, int32_t num_l2);
+int miclip_eval_reset(void* state, int32_t C, int32_t num_l2, void* stream);
+
+enum miclip_eval_l2 {
+  MICLIP_EVAL_L2_NONE = 0,      /* no L2 roll-up; l3_to_l2 must be NULL */
+  MICLIP_EVAL_L2_ARGMAX = 1,    /* L2 prediction = l3_to_l2[prediction] (mode "argmax") */
+  MICLIP_EVAL_L2_SUM = 2,       /* mode "logits", reduce "sum" */
+  MICLIP_EVAL_L2_MEAN = 3,      /* reduce "mean": sum / max(group size, 1) */
+  MICLIP_EVAL_L2_LOGSUMEXP = 4  /* reduce "logsumexp": running logaddexp from -inf */
+};
+#define MICLIP_EVAL_LOGITS_IN 1u /* flags: `logits` is read, not computed */
+
+/* One batch. feats [B, E] (f_dtype MICLIP_F32 / MICLIP_FP16 / MICLIP_BF16, widened
+ * in the load, 16-byte aligned), text_weights fp32 [E, C], labels int64 [B]:
+ *   logits[b, c] = scale * (feats[b] . text_weights[:, c]) / max(|feats[b]|, 1e-12),
+ * bitwise the logits of miclip_zero_shot(apply_proj = 0) on the fp32 features.
+ * With MICLIP_EVAL_LOGITS_IN in flags the [B, C] `logits` are an input instead
+ * (feats, text_weights, E unused): L2MetricsAccumulator.update's and
+ * aggregate_logits_to_l2's form. l3_to_l2: HOST int32 [C] (checked, then passed by
+ * value with the launch), NULL exactly when l2_mode is MICLIP_EVAL_L2_NONE.
+ * Per-row outputs, device memory: row_loss [B] (required) logsumexp(z) - z[label];
+ * row_pred [B], row_top3 [B, 3] class indices by value descending, lower index
+ * first among equals (torch.topk for distinct values); row_top3_prob [B, 3] their
+ * softmax probabilities; l2_pred [B]; l2_top3 [B, 3] (-1 beyond num_l2, and
+ * beyond the first in mode argmax); l2_logits [B, num_l2], the aggregated logits,
+ * group by group in ascending L3 id. `logits` [B, C] receives the logits when not
+ * an input. Every output but row_loss may be NULL.
+ * E % 16 == 0, 16 <= E <= 1024, 3 <= C <= 1024, 1 <= num_l2 <= C, every l3_to_l2
+ * entry in [0, num_l2), B >= 1: anything else is MICLIP_EINVAL before any launch.
+ * A row whose label is outside [0, C) is skipped by every accumulator (word 7
+ * counts it) and its row_loss is 0; nothing is indexed with it. */
+int miclip_eval_batch(const void* feats, int32_t f_dtype, const float* text_weights,
+                      const int64_t* labels, int32_t B, int32_t E, int32_t C, float scale,
+                      const int32_t* l3_to_l2, int32_t num_l2, int32_t l2_mode, uint32_t flags,
+                      void* state, float* logits, float* row_loss, int32_t* row_pred,
+                      int32_t* row_top3, float* row_top3_prob, int32_t* l2_pred,
+                      int32_t* l2_top3, float* l2_logits, void* stream);
+
 /* Batch split of encode_image over the caller's stream and one handle-owned
  * stream (fork/join by events, so the call stays stream-ordered and
  * graph-capturable): 1 = off, 2..4 = that many parts (default 2; a part is
