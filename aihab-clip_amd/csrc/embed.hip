@@ -294,30 +294,43 @@ __global__ __launch_bounds__(256) void head_logits_kernel(const float* __restric
   }
 }
 
-// The top-k classes of each logits row (largest first, ties -> lower index; the
-// order torch.topk(sorted=True) returns for distinct values), one wave per row:
-// pick j is the arg-max over the classes strictly after pick j - 1 in (value
-// descending, index ascending) order, so no state but the previous pick is kept
-// and the row (L2-resident, C floats) is re-read per pick.
+// The rank order of the top-k: (av, ai) comes before (bv, bi) when av is NaN and bv
+// is not, else when av > bv, else -- both NaN, or equal values -- when ai < bi. A
+// strict total order over the entries of a row (torch.topk's: NaN above every
+// number, the lower index first among equals).
+__device__ __forceinline__ bool ranks_before(float av, int ai, float bv, int bi) {
+  const bool an = av != av, bn = bv != bv;
+  if (an != bn) return an;
+  if (!an && av != bv) return av > bv;
+  return ai < bi;
+}
+
+// The top-k classes of each logits row (largest first, NaN above every number,
+// ties and NaNs -> lower index first: the order torch.topk(sorted=True) returns),
+// one wave per row: pick j is the first class strictly after pick j - 1 in
+// ranks_before's order, so no state but the previous pick is kept and the row
+// (L2-resident, C floats) is re-read per pick. The order is total, so for k <= C
+// every pick exists: the k indices are distinct and in [0, C) whatever the row
+// holds (+-inf, NaN, repeated values).
 __global__ __launch_bounds__(64) void topk_rows_kernel(const float* __restrict__ logits,
                                                        int32_t* __restrict__ topk, int C, int k) {
   const int lane = threadIdx.x;
   const float* lr = logits + (size_t)blockIdx.x * C;
-  float pv = INFINITY;
-  int pi = -1;
+  float pv = 0.f;
+  int pi = -1;   // no previous pick
   for (int j = 0; j < k; ++j) {
-    float bv = -INFINITY;
-    int bi = C;
+    float bv = 0.f;
+    int bi = C;    // C: nothing found yet
     for (int c = lane; c < C; c += 64) {
       const float v = lr[c];
-      const bool after = v < pv || (v == pv && c > pi);
-      if (after && (bi == C || v > bv)) { bv = v; bi = c; }   // ascending c: ties keep the lower
+      const bool after = pi < 0 || ranks_before(pv, pi, v, c);
+      if (after && (bi == C || ranks_before(v, c, bv, bi))) { bv = v; bi = c; }
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
       const float ov = __shfl_xor(bv, o);
       const int oi = __shfl_xor(bi, o);
-      if (oi < C && (bi == C || ov > bv || (ov == bv && oi < bi))) { bv = ov; bi = oi; }
+      if (oi < C && (bi == C || ranks_before(ov, oi, bv, bi))) { bv = ov; bi = oi; }
     }
     if (lane == 0) topk[(size_t)blockIdx.x * k + j] = bi;
     pv = bv;

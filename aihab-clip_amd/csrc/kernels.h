@@ -137,6 +137,9 @@ hipError_t row_l2norm(float* x, int R, int D, hipStream_t s);
 // zero-shot head: f = normalize(x @ proj) (proj may be null -> f = normalize(x));
 // logits = scale * f @ tw ([E, C], E % 16 == 0) on the f32 MFMA with the row norm
 // fused (head_logits_kernel); topk indices (sorted, largest first; topk_rows_kernel).
+// The top-k order is torch.topk's: NaN ranks above every number (+inf included),
+// and among NaNs or equal values the lower index comes first; for k <= C the k
+// indices of a row are distinct and lie in [0, C) whatever the logits hold.
 // With proj, scratch (fp32 [B, E]) receives the projection, which runs first as
 // a chip-wide f32-MFMA kernel (head_proj_kernel, also behind rowvec_matmul).
 hipError_t zero_shot(const float* x, const float* proj, const float* tw, float* logits,
@@ -149,7 +152,10 @@ hipError_t row_norms(const float* x, int N, int D, float* norms, hipStream_t s);
 hipError_t div_rows(const float* x, const float* norms, int N, int D, float eps, float* out,
                     hipStream_t s);
 // class k's rows are order[offsets[k] .. offsets[k+1]) (ascending sample order);
-// sums [K,D] = per-class sums in that order; centroids = normalize(sums / count).
+// sums [K,D] = per-class sums in that order (a strict left-to-right fp32 sum, bit-
+// equal to a CPU loop over the samples); centroids = normalize(sums / count). An
+// empty class (offsets[k] == offsets[k+1]) has a sums row and a centroid row of
+// exact zeros and changes no other class's rows.
 hipError_t class_centroids(const float* x, const int32_t* order, const int32_t* offsets, int K,
                            int D, float eps, float* sums, float* centroids, hipStream_t s);
 // sim[s,p] = (x[s] . protos[p]) * inv_nx[s] * inv_np[p] (null -> 1); per sample:

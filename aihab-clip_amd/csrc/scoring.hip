@@ -61,12 +61,15 @@ __global__ __launch_bounds__(64) void class_sums_kernel(const float* __restrict_
   sums[(size_t)k * D + col] = acc;
 }
 
-// means = sums / count; out = means / max(||means||, eps)  (F.normalize)
+// means = sums / count; out = means / max(||means||, eps)  (F.normalize). An empty
+// class (count 0; the reference refuses one, outlier_cleaning.py:275) has sums 0 and
+// is divided by 1: its centroid row is all zeros, not 0 / 0.
 __global__ __launch_bounds__(64) void centroid_kernel(const float* __restrict__ sums,
                                                       const int32_t* __restrict__ offsets, int D,
                                                       float eps, float* __restrict__ out) {
   const int k = blockIdx.x;
-  const float cnt = (float)(offsets[k + 1] - offsets[k]);
+  const int n = offsets[k + 1] - offsets[k];
+  const float cnt = (float)(n > 0 ? n : 1);
   const float* s = sums + (size_t)k * D;
   float* o = out + (size_t)k * D;
   float n2 = 0.f;

@@ -150,19 +150,42 @@ def test_multi_prototype_matches_reference(fx, tag):
 
 @pytest.mark.gpu
 def test_class_sums_are_sequential_order_exact():
-    """class_centroids sums rows in ascending sample order: bit-equal to a CPU index_add_."""
+    """class_centroids sums rows in ascending sample order: the `sums` buffer is bit-equal
+    to a strict sequential fp32 accumulation on the CPU (a numpy float32 loop over the
+    samples, which is also what a CPU index_add_ gives)."""
     if not torch.cuda.is_available():
         pytest.skip("no HIP device")
+    import ctypes
+    from miclip import _lib
     from miclip.outliers import _class_centroids
     g = torch.Generator().manual_seed(3)
     x = torch.randn(5000, 768, generator=g)
     inv = torch.randint(0, 7, (5000,), generator=g)
+    seq = np.zeros((7, 768), dtype=np.float32)
+    xn = x.numpy()
+    for i, k in enumerate(inv.tolist()):       # ascending sample order, one fp32 add each
+        seq[k] = seq[k] + xn[i]
     sums = torch.zeros(7, 768).index_add_(0, inv, x)
+    assert np.array_equal(sums.numpy().view(np.uint32), seq.view(np.uint32))
     counts = torch.bincount(inv, minlength=7)
     ref = torch.nn.functional.normalize(sums / counts[:, None].float(), dim=-1, eps=1e-12)
-    cent, cnt = _class_centroids(x.cuda(), inv.numpy(), 7, 1e-12)
+    xd = x.cuda()
+    cent, cnt = _class_centroids(xd, inv.numpy(), 7, 1e-12)
     assert np.array_equal(cnt, counts.numpy())
     assert (cent.cpu() - ref).abs().max().item() <= 1e-6
+    # the sums themselves, read back through the C ABI (the CSR as _class_centroids builds it)
+    order = torch.from_numpy(np.argsort(inv.numpy(), kind="stable").astype(np.int32)).cuda()
+    off = torch.from_numpy(np.concatenate([[0], np.cumsum(cnt)]).astype(np.int32)).cuda()
+    got_s, got_c = torch.empty(7, 768, device="cuda"), torch.empty(7, 768, device="cuda")
+    p = lambda t: ctypes.c_void_p(t.data_ptr())   # noqa: E731
+    _lib.check(_lib.load_library().miclip_class_centroids(
+        p(xd), p(order), p(off), 7, 768, 1e-12, p(got_s), p(got_c), _lib.stream_handle()),
+        "miclip_class_centroids")
+    got = got_s.cpu().numpy()
+    print(f"sums differing in bits from the sequential fp32 loop: "
+          f"{int((got.view(np.uint32) != seq.view(np.uint32)).sum())} of {got.size}")
+    assert np.array_equal(got.view(np.uint32), seq.view(np.uint32))
+    assert torch.equal(got_c, cent)
 
 
 @pytest.mark.gpu
