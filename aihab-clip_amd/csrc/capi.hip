@@ -1022,6 +1022,57 @@ int miclip_proto_scores(const float* x, const float* protos, const int32_t* owne
   return 0;
 }
 
+// the limits the two k-means entry points share; false (and `why`) when one is broken
+static bool kmeans_args_ok(int32_t D, int32_t Pn, int32_t k_max, std::string& why) {
+  if (D < 1 || D > 1024) why = "D must be in 1..1024, got " + std::to_string(D);
+  else if (Pn < 1 || Pn > 65535) why = "Pn must be in 1..65535, got " + std::to_string(Pn);
+  else if (k_max < 2 || k_max > 16) why = "k_max must be in 2..16, got " + std::to_string(k_max);
+  return why.empty();
+}
+
+int64_t miclip_kmeans_scratch_bytes(int64_t total_rows) {
+  return total_rows < 1 ? 0 : total_rows * (int64_t)sizeof(float);
+}
+
+int miclip_kmeans_seed(const float* x, const int32_t* order, const int32_t* offsets, int32_t D,
+                       const int32_t* prob_class, const int32_t* prob_k, const int32_t* prob_off,
+                       int32_t Pn, int32_t k_max, const float* u, float* scratch, int32_t* picks,
+                       float* centres, void* stream) {
+  const std::pair<const void*, const char*> ptrs[] = {
+      {x, "x"}, {order, "order"}, {offsets, "offsets"}, {prob_class, "prob_class"},
+      {prob_k, "prob_k"}, {prob_off, "prob_off"}, {u, "u"}, {scratch, "scratch"},
+      {picks, "picks"}, {centres, "centres"}};
+  for (const auto& a : ptrs)
+    if (!a.first) return fail(MICLIP_EINVAL, std::string("null argument: ") + a.second);
+  std::string why;
+  if (!kmeans_args_ok(D, Pn, k_max, why)) return fail(MICLIP_EINVAL, why);
+  MICLIP_HIP(kmeans_seed(x, order, offsets, D, prob_class, prob_k, prob_off, Pn, k_max, u, scratch,
+                         picks, centres, (hipStream_t)stream));
+  return 0;
+}
+
+int miclip_kmeans_lloyd(const float* x, const int32_t* order, const int32_t* offsets, int32_t D,
+                        const int32_t* prob_class, const int32_t* prob_k, const int32_t* prob_off,
+                        int32_t Pn, int32_t k_max, const float* tol, int32_t max_iter,
+                        float* scratch, float* centres, int32_t* labels, float* inertia,
+                        int32_t* n_iter, int32_t* strict, int32_t* counts, void* stream) {
+  const std::pair<const void*, const char*> ptrs[] = {
+      {x, "x"}, {order, "order"}, {offsets, "offsets"}, {prob_class, "prob_class"},
+      {prob_k, "prob_k"}, {prob_off, "prob_off"}, {tol, "tol"}, {scratch, "scratch"},
+      {centres, "centres"}, {labels, "labels"}, {inertia, "inertia"}, {n_iter, "n_iter"},
+      {counts, "counts"}};
+  for (const auto& a : ptrs)
+    if (!a.first) return fail(MICLIP_EINVAL, std::string("null argument: ") + a.second);
+  std::string why;
+  if (!kmeans_args_ok(D, Pn, k_max, why)) return fail(MICLIP_EINVAL, why);
+  if (max_iter < 1)
+    return fail(MICLIP_EINVAL, "max_iter must be >= 1, got " + std::to_string(max_iter));
+  MICLIP_HIP(kmeans_lloyd(x, order, offsets, D, prob_class, prob_k, prob_off, Pn, k_max, tol,
+                          max_iter, scratch, centres, labels, inertia, n_iter, strict, counts,
+                          (hipStream_t)stream));
+  return 0;
+}
+
 int miclip_prolip_grad(const void* x, int32_t x_dtype, const int64_t* labels, int32_t n, int32_t D,
                        int32_t E, int32_t C, const float* text_weights, const float* P,
                        int32_t G, float scale, float* dZ, float* partials, void* stream) {

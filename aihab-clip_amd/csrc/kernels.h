@@ -166,6 +166,27 @@ hipError_t proto_scores(const float* x, const float* protos, const int32_t* owne
                         int P, int D, float* own_best, int32_t* own_arg, float* other_best,
                         hipStream_t s);
 
+// ---- device k-means for the multi-prototype scorer (kmeans.hip), fp32 ----
+// Pn problems, one workgroup each: problem p clusters class prob_class[p]'s rows
+// (order / offsets as in class_centroids) into prob_k[p] <= k_max clusters; its
+// per-row outputs and scratch start at prob_off[p] (floats / int32s). 1 <= D <= 1024,
+// 2 <= k_max <= 16, 1 <= Pn <= 65535, max_iter >= 1, else hipErrorInvalidValue.
+// kmeans_seed: k-means++ from the uniforms u [Pn, 16] -> picks [Pn, 16] (positions
+// inside the class) and centres [Pn, 16, D]; scratch: one float per problem row.
+hipError_t kmeans_seed(const float* x, const int32_t* order, const int32_t* offsets, int D,
+                       const int32_t* prob_class, const int32_t* prob_k, const int32_t* prob_off,
+                       int Pn, int k_max, const float* u, float* scratch, int32_t* picks,
+                       float* centres, hipStream_t s);
+// kmeans_lloyd: scikit-learn's Lloyd loop from centres (in/out), at most max_iter
+// iterations, stop on unchanged labels (strict) or centre shift <= tol[p]; labels
+// (per problem row), inertia / n_iter / strict [Pn] (strict may be null), counts [Pn, 16].
+hipError_t kmeans_lloyd(const float* x, const int32_t* order, const int32_t* offsets, int D,
+                        const int32_t* prob_class, const int32_t* prob_k,
+                        const int32_t* prob_off, int Pn, int k_max, const float* tol,
+                        int max_iter, float* scratch, float* centres, int32_t* labels,
+                        float* inertia, int32_t* n_iter, int32_t* strict, int32_t* counts,
+                        hipStream_t s);
+
 // ---- ProLIP projector training on cached features (prolip.hip), fp32 ----
 // One optimiser step of G configurations that share x [n, D] (x_dtype kIn32 / kF16 /
 // kBF16, 16-B aligned), labels [n] in [0, C), W [E, C] and P0 [D, E] and differ in

@@ -45,6 +45,7 @@ EXPORTS = (
     "miclip_op_gemm", "miclip_op_gemm_splitk", "miclip_op_ln_stats", "miclip_op_ln_fold", "miclip_op_gemm_ln",
     "miclip_op_layernorm", "miclip_op_attention", "miclip_op_attention_q0", "miclip_op_im2col", "miclip_preprocess",
     "miclip_row_norms", "miclip_class_centroids", "miclip_proto_scores",
+    "miclip_kmeans_scratch_bytes", "miclip_kmeans_seed", "miclip_kmeans_lloyd",
     "miclip_prolip_grad", "miclip_prolip_adam",
     "miclip_eval_state_bytes", "miclip_eval_reset", "miclip_eval_batch",
     "miclip_mx_scale_bytes", "miclip_op_quant_mx", "miclip_op_gemm_mx", "miclip_op_gemm_mx_v", "miclip_op_layernorm_mx",
@@ -147,6 +148,11 @@ def load_library(path: str = None):
         "miclip_class_centroids": ([vp, vp, vp, i32, i32, f32, vp, vp, vp], ctypes.c_int),
         "miclip_proto_scores": ([vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp],
                                 ctypes.c_int),
+        "miclip_kmeans_scratch_bytes": ([i64], i64),
+        "miclip_kmeans_seed": ([vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp],
+                               ctypes.c_int),
+        "miclip_kmeans_lloyd": ([vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, vp,
+                                 vp, vp, vp, vp], ctypes.c_int),
         "miclip_prolip_grad": ([vp, i32, vp, i32, i32, i32, i32, vp, vp, i32, f32, vp, vp, vp],
                                ctypes.c_int),
         "miclip_prolip_adam": ([vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, f32, f32,

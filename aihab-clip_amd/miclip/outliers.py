@@ -11,12 +11,20 @@ kernels of csrc/scoring.hip through the C ABI:
   * cosine to own centroid            miclip_proto_scores     (:293-383)
   * nearest own-class prototype and
     best other-class prototype        miclip_proto_scores     (:557-760)
+  * k-means fit of the prototypes     miclip_kmeans_seed /
+    (compute_prototypes(kmeans=       miclip_kmeans_lloyd     (:511-541)
+    "device"))
 
 What stays on the host, as in the reference: label bookkeeping
-(torch.unique), the spherical k-means fit of compute_prototypes (scikit-learn
-KMeans with the reference's parameters, :488-498) and the pandas ranking /
-quantile / sort post-processing. Embeddings live on the HIP device; there is
-no CPU fallback.
+(torch.unique) and the pandas ranking / quantile / sort post-processing. The
+k-means fit of compute_prototypes has two backends: kmeans="sklearn" (the
+default) is the reference's scikit-learn KMeans with its parameters (:488-498),
+one host fit per class; kmeans="device" runs every (class, restart) pair as one
+problem of a single seeding launch and a single Lloyd launch (csrc/kmeans.hip),
+with no host round trip and without scikit-learn, which only the "sklearn"
+backend imports. The two backends draw different seeds, so on unstructured data
+they may settle in different, equally valid local optima. Embeddings live on
+the HIP device; there is no CPU fallback.
 """
 from dataclasses import dataclass
 from pathlib import Path
@@ -147,6 +155,13 @@ def _row_norms(x: torch.Tensor, eps: float = 1e-12, normalize: bool = False):
 
 def _class_centroids(x: torch.Tensor, inv: np.ndarray, K: int, eps: float):
     """normalize(per-class mean) with the rows of each class summed in sample order."""
+    cent, counts, _ = _class_layout(x, inv, K, eps)
+    return cent, counts
+
+
+def _class_layout(x: torch.Tensor, inv: np.ndarray, K: int, eps: float):
+    """_class_centroids plus the device class layout it was computed on:
+    (centroids, counts, {"order", "offsets" (device int32), "sums" [K, D]})."""
     lib = _lib.load_library()
     order = np.argsort(inv, kind="stable").astype(np.int32)
     counts = np.bincount(inv, minlength=K)
@@ -161,7 +176,7 @@ def _class_centroids(x: torch.Tensor, inv: np.ndarray, K: int, eps: float):
         _lib.check(lib.miclip_class_centroids(_ptr(x), _ptr(order_d), _ptr(off_d), K, D,
                                               float(eps), _ptr(sums), _ptr(cent), _stream(dev)),
                    "miclip_class_centroids")
-    return cent, counts
+    return cent, counts, {"order": order_d, "offsets": off_d, "sums": sums}
 
 
 def _proto_scores(x, protos, owner, cls, inv_nx=None, inv_np=None):
@@ -178,6 +193,97 @@ def _proto_scores(x, protos, owner, cls, inv_nx=None, inv_np=None):
                                            _ptr(arg), _ptr(oth), _stream(dev)),
                    "miclip_proto_scores")
     return own, arg, oth
+
+
+_KMEANS_MAX_K, _KMEANS_MAX_D, _KMEANS_SLOTS = 16, 1024, 16   # limits of csrc/kmeans.hip
+
+
+def _kmeans_table(counts, classes, ks, n_init, dev):
+    """Problem table of miclip_kmeans_*: n_init consecutive problems per class of
+    `classes` (indices into the class layout) with ks[i] clusters; a problem's rows
+    of the per-row buffers start at "off"."""
+    prob_class = np.repeat(np.asarray(classes, np.int64), n_init)
+    prob_k = np.repeat(np.asarray(ks, np.int64), n_init)
+    rows = np.asarray(counts, np.int64)[prob_class]
+    total = int(rows.sum())
+    if total >= 2 ** 31:
+        raise ValueError(f"k-means problem table too large: {total} rows over all restarts.")
+    prob_off = np.concatenate([[0], np.cumsum(rows)[:-1]])
+    as_dev = lambda a: torch.from_numpy(a.astype(np.int32)).to(dev)   # noqa: E731
+    return {"cls": as_dev(prob_class), "k": as_dev(prob_k), "off": as_dev(prob_off),
+            "Pn": int(prob_class.size), "k_max": int(prob_k.max()), "total": total}
+
+
+def _kmeans_seed(x, layout, table, u, scratch=None):
+    """miclip_kmeans_seed: (picks [Pn, 16] int32, centres [Pn, 16, D]) from uniforms u [Pn, 16]."""
+    lib = _lib.load_library()
+    dev, D, Pn = x.device, x.shape[1], table["Pn"]
+    if scratch is None:
+        scratch = torch.empty(table["total"], device=dev, dtype=torch.float32)
+    picks = torch.empty(Pn, _KMEANS_SLOTS, device=dev, dtype=torch.int32)
+    centres = torch.zeros(Pn, _KMEANS_SLOTS, D, device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        _lib.check(lib.miclip_kmeans_seed(_ptr(x), _ptr(layout["order"]), _ptr(layout["offsets"]),
+                                          D, _ptr(table["cls"]), _ptr(table["k"]),
+                                          _ptr(table["off"]), Pn, table["k_max"], _ptr(u),
+                                          _ptr(scratch), _ptr(picks), _ptr(centres), _stream(dev)),
+                   "miclip_kmeans_seed")
+    return picks, centres
+
+
+def _kmeans_lloyd(x, layout, table, tol, max_iter, centres, scratch=None):
+    """miclip_kmeans_lloyd from `centres` [Pn, 16, D], which is updated in place."""
+    lib = _lib.load_library()
+    dev, D, Pn = x.device, x.shape[1], table["Pn"]
+    if scratch is None:
+        scratch = torch.empty(table["total"], device=dev, dtype=torch.float32)
+    out = {"centres": centres,
+           "labels": torch.empty(table["total"], device=dev, dtype=torch.int32),
+           "inertia": torch.empty(Pn, device=dev, dtype=torch.float32),
+           "n_iter": torch.empty(Pn, device=dev, dtype=torch.int32),
+           "strict": torch.empty(Pn, device=dev, dtype=torch.int32),
+           "counts": torch.empty(Pn, _KMEANS_SLOTS, device=dev, dtype=torch.int32)}
+    with torch.cuda.device(dev):
+        _lib.check(lib.miclip_kmeans_lloyd(_ptr(x), _ptr(layout["order"]), _ptr(layout["offsets"]),
+                                           D, _ptr(table["cls"]), _ptr(table["k"]),
+                                           _ptr(table["off"]), Pn, table["k_max"], _ptr(tol),
+                                           int(max_iter), _ptr(scratch), _ptr(centres),
+                                           _ptr(out["labels"]), _ptr(out["inertia"]),
+                                           _ptr(out["n_iter"]), _ptr(out["strict"]),
+                                           _ptr(out["counts"]), _stream(dev)),
+                   "miclip_kmeans_lloyd")
+    return out
+
+
+def _kmeans_class_tol(x, layout, counts, rel=1e-4):
+    """scikit-learn's scaled tolerance per class, on the device: rel * mean over the
+    columns of the column variance = rel * (sum |x|^2 / n - |sum x / n|^2) / D, from the
+    class sums of miclip_class_centroids and the row norms (fp64, class order)."""
+    norms, _ = _row_norms(x)
+    off = layout["offsets"].long()
+    sq = norms.double().square().index_select(0, layout["order"].long())
+    run = torch.cat([sq.new_zeros(1), sq.cumsum(0)])
+    n = torch.from_numpy(np.maximum(np.asarray(counts, np.float64), 1.0)).to(x.device)
+    ssq = run.index_select(0, off[1:]) - run.index_select(0, off[:-1])
+    mean_sq = (layout["sums"].double() / n[:, None]).square().sum(dim=1)
+    return (rel * (ssq / n - mean_sq) / x.shape[1]).clamp_min(0.0).float()
+
+
+def _kmeans_fit_device(x, layout, counts, classes, ks, n_init, max_iter, random_state):
+    """n_init k-means++ / Lloyd fits of every class of `classes`, in two launches. Returns
+    the Lloyd outputs with "inertia" / "n_iter" shaped [len(classes), n_init] next to the
+    flat per-problem "centres" [Pn, 16, D], "labels", "counts", and the "table"."""
+    dev = x.device
+    table = _kmeans_table(counts, classes, ks, n_init, dev)
+    u = np.random.default_rng(random_state).random((table["Pn"], _KMEANS_SLOTS), dtype=np.float32)
+    tol = _kmeans_class_tol(x, layout, counts).index_select(0, table["cls"].long()).contiguous()
+    scratch = torch.empty(table["total"], device=dev, dtype=torch.float32)
+    picks, centres = _kmeans_seed(x, layout, table, torch.from_numpy(u).to(dev), scratch)
+    fit = _kmeans_lloyd(x, layout, table, tol, max_iter, centres, scratch)
+    fit["inertia"] = fit["inertia"].view(len(classes), n_init)
+    fit["n_iter"] = fit["n_iter"].view(len(classes), n_init)
+    fit.update(picks=picks, table=table, tol=tol)
+    return fit
 
 
 def _device(device):
@@ -323,44 +429,50 @@ class MultiPrototypeScorer(SingleCentroidScorer):
                          device=device)
         self._prototypes: Optional[MultiPrototypeResult] = None
         self._prototype_config = None
+        self._kmeans_fit = None   # device backend: the last fit's per-restart outputs
 
     def compute_prototypes(self, *, k_mode: str = "heuristic", k_fixed: int = 2, k_max: int = 4,
                            min_samples_per_proto: int = 15, random_state: int = 0,
-                           n_init: int = 10, max_iter: int = 100) -> MultiPrototypeResult:
+                           n_init: int = 10, max_iter: int = 100,
+                           kmeans: str = "sklearn") -> MultiPrototypeResult:
+        """Per-class prototypes. kmeans="sklearn" fits each class on the host with
+        scikit-learn (the reference's path); kmeans="device" fits every class and
+        restart in two launches of csrc/kmeans.hip (k-means++ seeds drawn from
+        numpy.random.default_rng(random_state), the restart with the lowest inertia
+        wins, the first one among equals) and needs k <= 16 and D <= 1024."""
         if k_mode not in {"heuristic", "fixed"}:
             raise ValueError(f"Unsupported k_mode '{k_mode}'. Expected one of: heuristic, fixed.")
+        if kmeans not in {"sklearn", "device"}:
+            raise ValueError(f"Unsupported kmeans '{kmeans}'. Expected one of: sklearn, device.")
         for name, v in (("k_fixed", k_fixed), ("k_max", k_max),
                         ("min_samples_per_proto", min_samples_per_proto), ("n_init", n_init),
                         ("max_iter", max_iter)):
             if int(v) < 1:
                 raise ValueError(f"{name} must be >= 1, got {v}.")
         config = (str(k_mode), int(k_fixed), int(k_max), int(min_samples_per_proto),
-                  int(random_state), int(n_init), int(max_iter))
+                  int(random_state), int(n_init), int(max_iter), str(kmeans))
         if self._prototypes is not None and self._prototype_config == config:
             return self._prototypes
-        try:
-            from sklearn.cluster import KMeans
-        except ImportError as exc:
-            raise ImportError("scikit-learn is required for multi-prototype scoring. "
-                              "Install it to use MultiPrototypeScorer.") from exc
+        if kmeans == "sklearn":
+            try:
+                from sklearn.cluster import KMeans
+            except ImportError as exc:
+                raise ImportError("scikit-learn is required for multi-prototype scoring with "
+                                  "kmeans='sklearn'. Install it, or use kmeans='device'.") from exc
         emb = self._get_normalized_embeddings()
         uniq, inv = self._classes()
         if int(uniq.numel()) == 0:
             raise ValueError("No labels present to compute prototypes.")
         K = int(uniq.numel())
-        means, counts = _class_centroids(emb, inv, K, self.eps)   # the k = 1 prototypes
+        means, counts, layout = _class_layout(emb, inv, K, self.eps)   # the k = 1 prototypes
+        if kmeans == "device":
+            return self._compute_prototypes_device(emb, uniq, inv, means, counts, layout, config)
         prototypes, class_counts, prototype_counts, k_per_class = {}, {}, {}, {}
         for ci in range(K):
             label_id = int(uniq[ci])
             n_c = int(counts[ci])
             class_counts[label_id] = n_c
-            if k_mode == "heuristic":
-                base_k = 1 if n_c < 20 else 3 if n_c < 100 else 4 if n_c < 200 else \
-                    5 if n_c < 300 else 6
-            else:
-                base_k = int(k_fixed)
-            base_k = min(base_k, int(k_max))
-            k_c = max(1, int(min(base_k, n_c, max(1, n_c // int(min_samples_per_proto)))))
+            k_c = self._class_k(n_c, config)
             if k_c == 1:
                 center = means[ci:ci + 1]
                 if not bool(torch.isfinite(center).all()):
@@ -386,6 +498,82 @@ class MultiPrototypeScorer(SingleCentroidScorer):
             prototypes[label_id] = centers
             prototype_counts[label_id] = [int(v) for v in cnt]
             k_per_class[label_id] = k_c
+        self._prototypes = MultiPrototypeResult(prototypes=prototypes, class_counts=class_counts,
+                                                prototype_counts=prototype_counts,
+                                                k_per_class=k_per_class, dim=self.dim)
+        self._prototype_config = config
+        return self._prototypes
+
+    @staticmethod
+    def _class_k(n_c: int, config) -> int:
+        """Prototypes of a class of n_c rows (tools/outlier_cleaning.py:470-486)."""
+        k_mode, k_fixed, k_max, min_samples_per_proto = config[:4]
+        if k_mode == "heuristic":
+            base_k = 1 if n_c < 20 else 3 if n_c < 100 else 4 if n_c < 200 else \
+                5 if n_c < 300 else 6
+        else:
+            base_k = int(k_fixed)
+        base_k = min(base_k, int(k_max))
+        return max(1, int(min(base_k, n_c, max(1, n_c // int(min_samples_per_proto)))))
+
+    def _compute_prototypes_device(self, emb, uniq, inv, means, counts, layout, config):
+        """compute_prototypes(kmeans="device"): every class with k > 1, times n_init
+        restarts, is one problem of one miclip_kmeans_seed and one miclip_kmeans_lloyd
+        launch. Nothing is read back before the result is assembled: the winning
+        restart is gathered on the device (torch.argmin: the first minimum), the
+        prototype counts come from one miclip_proto_scores call over all rows, and a
+        single copy at the end fetches those counts and the finiteness flags."""
+        random_state, n_init, max_iter = config[4:7]
+        dev, D, K = self.device, self.dim, int(uniq.numel())
+        ks = [self._class_k(int(counts[ci]), config) for ci in range(K)]
+        if max(ks) > _KMEANS_MAX_K:
+            raise ValueError(f"kmeans='device' supports at most {_KMEANS_MAX_K} prototypes per "
+                             f"class, got {max(ks)}.")
+        if D > _KMEANS_MAX_D and max(ks) > 1:
+            raise ValueError(f"kmeans='device' supports embedding dims up to {_KMEANS_MAX_D}, "
+                             f"got {D}.")
+        multi = [ci for ci in range(K) if ks[ci] > 1]
+        blocks = [means[ci:ci + 1] for ci in range(K)]
+        self._kmeans_fit = None
+        if multi:
+            fit = _kmeans_fit_device(emb, layout, counts, multi, [ks[ci] for ci in multi],
+                                     int(n_init), int(max_iter), int(random_state))
+            best = fit["inertia"].argmin(dim=1)                                   # [len(multi)]
+            chosen = torch.arange(len(multi), device=dev) * int(n_init) + best
+            centres = fit["centres"].index_select(0, chosen)                      # [m, 16, D]
+            rows = torch.cat([centres[i, :ks[ci]] for i, ci in enumerate(multi)]).contiguous()
+            _, rows = _row_norms(rows, self.eps, normalize=True)
+            at = 0
+            for ci in multi:
+                blocks[ci] = rows[at:at + ks[ci]]
+                at += ks[ci]
+            fit["chosen"] = best
+            fit["classes"] = [int(uniq[ci]) for ci in multi]
+            self._kmeans_fit = fit
+        protos = torch.cat(blocks).contiguous()
+        first = np.concatenate([[0], np.cumsum(ks)])
+        owner = torch.from_numpy(np.repeat(np.arange(K), ks).astype(np.int32)).to(dev)
+        cls = torch.from_numpy(inv.astype(np.int32)).to(dev)
+        # re-assign by cosine (rows and prototypes are unit vectors) for the prototype counts
+        _, arg, _ = _proto_scores(emb, protos, owner, cls)
+        sizes = torch.zeros(protos.shape[0], device=dev, dtype=torch.int64)
+        sizes.scatter_add_(0, arg.long(), torch.ones_like(arg, dtype=torch.int64))
+        finite = torch.isfinite(protos).all(dim=1)
+        host = torch.cat([sizes, finite.long()]).cpu().numpy()      # the one copy to the host
+        sizes_h, finite_h = host[:protos.shape[0]], host[protos.shape[0]:]
+        prototypes, class_counts, prototype_counts, k_per_class = {}, {}, {}, {}
+        for ci in range(K):
+            label_id = int(uniq[ci])
+            lo, hi = int(first[ci]), int(first[ci + 1])
+            if not finite_h[lo:hi].all():
+                raise ValueError(f"Non-finite prototype found for class {label_id} (k=1)."
+                                 if ks[ci] == 1 else
+                                 f"Non-finite prototype centers found for class {label_id}.")
+            prototypes[label_id] = blocks[ci]
+            class_counts[label_id] = int(counts[ci])
+            prototype_counts[label_id] = ([int(counts[ci])] if ks[ci] == 1 else
+                                          [int(v) for v in sizes_h[lo:hi]])
+            k_per_class[label_id] = ks[ci]
         self._prototypes = MultiPrototypeResult(prototypes=prototypes, class_counts=class_counts,
                                                 prototype_counts=prototype_counts,
                                                 k_per_class=k_per_class, dim=self.dim)

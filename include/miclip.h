@@ -216,6 +216,52 @@ int miclip_proto_scores(const float* x, const float* protos, const int32_t* owne
                         int32_t P, int32_t D, float* own_best, int32_t* own_arg,
                         float* other_best, void* stream);
 
+/* ---- device k-means for the multi-prototype scorer, fp32 ----
+ * Replace the per-class KMeans(n_init, max_iter).fit of compute_prototypes
+ * (tools/outlier_cleaning.py:511-541) by two launches over a problem table: a
+ * launch runs Pn problems, one workgroup each. Problem p clusters the rows of
+ * class prob_class[p] -- order[offsets[c] .. offsets[c+1]), the class layout of
+ * miclip_class_centroids -- into prob_k[p] clusters; the restarts of a class are
+ * separate problems naming the same class. prob_off[p] is the problem's offset
+ * (in elements) into the per-row buffers `labels` and `scratch`, which hold one
+ * element per problem row (scratch: miclip_kmeans_scratch_bytes(total rows)
+ * bytes, shared by both calls). Per-problem blocks have 16 slots whatever k is:
+ * u / picks / counts [Pn, 16], centres [Pn, 16, D]; slots >= k are not written
+ * (counts: 0). Limits: 1 <= D <= 1024, 1 <= Pn <= 65535, 2 <= k_max <= 16 (the
+ * caller's bound on prob_k), max_iter >= 1; anything else is MICLIP_EINVAL with
+ * the argument named in miclip_last_error, before any launch. The table itself is
+ * device memory and is checked on the device: a problem with prob_k outside
+ * 2..16 or fewer rows than clusters is skipped (picks = -1, n_iter = -1). All
+ * pointers are caller-owned device memory; the calls are stream-ordered, never
+ * synchronise and never allocate. A problem's results are bit-identical run to
+ * run and do not depend on Pn or on its index.
+ *
+ * miclip_kmeans_seed (tools/outlier_cleaning.py:511-541, KMeans' init): plain
+ * k-means++ with one candidate per step from the uniforms u in [0, 1). Pick 0 is
+ * row min(floor(u0 n), n - 1); pick t is the first row whose inclusive prefix of
+ * mind[j] = min over the chosen centres of |x_j - c|^2 exceeds u_t * total, or the
+ * lowest row not yet chosen when total == 0. picks are positions inside the
+ * class; centres receives the chosen rows. */
+int64_t miclip_kmeans_scratch_bytes(int64_t total_rows);
+int miclip_kmeans_seed(const float* x, const int32_t* order, const int32_t* offsets, int32_t D,
+                       const int32_t* prob_class, const int32_t* prob_k, const int32_t* prob_off,
+                       int32_t Pn, int32_t k_max, const float* u, float* scratch, int32_t* picks,
+                       float* centres, void* stream);
+/* miclip_kmeans_lloyd (tools/outlier_cleaning.py:511-541, KMeans.fit's Lloyd
+ * loop, rule for rule as scikit-learn runs it): from the initial `centres`
+ * (in/out) at most max_iter iterations of {labels = argmin_j |x - c_j|^2, lowest
+ * index on a tie; centres = cluster means; an empty cluster, in ascending order,
+ * takes the row farthest from its own centre (lowest row among equals), which
+ * leaves its old cluster}; stop when the labels repeat (strict[p] = 1) or when
+ * sum_j |c_j_new - c_j_old|^2 <= tol[p] (strict[p] = 0, followed by one more
+ * labelling so labels match centres). inertia[p] = sum |x - c_label|^2, n_iter[p]
+ * the iterations run, counts the final cluster sizes. strict may be NULL. */
+int miclip_kmeans_lloyd(const float* x, const int32_t* order, const int32_t* offsets, int32_t D,
+                        const int32_t* prob_class, const int32_t* prob_k, const int32_t* prob_off,
+                        int32_t Pn, int32_t k_max, const float* tol, int32_t max_iter,
+                        float* scratch, float* centres, int32_t* labels, float* inertia,
+                        int32_t* n_iter, int32_t* strict, int32_t* counts, void* stream);
+
 /* ---- ProLIP projector training on the pre-projection feature cache, fp32 ----
  * One optimiser step of G configurations (the (lr, lambda) grid of search_lr,
  * or G = 1) per pair of calls. They share x [n, D] (x_dtype MICLIP_F32,
