@@ -989,6 +989,21 @@ int miclip_preprocess(miclip_model* m, const uint8_t* pixels, const miclip_image
   return 0;
 }
 
+int miclip_preprocess_aug(miclip_model* m, const uint8_t* pixels, const miclip_image_desc* descs,
+                          const miclip_aug_desc* augs, int32_t B, void* out, int32_t out_kind,
+                          void* stream) {
+  if (!m || !pixels || !descs || !augs || !out || B < 1)
+    return fail(MICLIP_EINVAL, "bad argument to preprocess_aug");
+  if (!m->pre) m->pre = pre_cache_create();
+  char err[256] = {0};
+  const hipError_t e = preprocess_aug(m->pre, pixels, descs, augs, B, m->cfg.image_resolution,
+                                      out_kind, out, (hipStream_t)stream, err, sizeof(err));
+  if (e != hipSuccess)
+    return fail(e == hipErrorInvalidValue ? MICLIP_EINVAL : MICLIP_EHIP,
+                err[0] ? std::string(err) : std::string("preprocess_aug: ") + hipGetErrorString(e));
+  return 0;
+}
+
 int miclip_clock_probe(uint64_t* out, int32_t n_wg, void* stream) {
   if (!out || n_wg < 1 || n_wg > 4096) return fail(MICLIP_EINVAL, "bad argument to clock_probe");
   MICLIP_HIP(clock_probe((unsigned long long*)out, n_wg, (hipStream_t)stream));

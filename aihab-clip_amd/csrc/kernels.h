@@ -244,5 +244,10 @@ PreCache* pre_cache_create();
 void pre_cache_destroy(PreCache* c);
 hipError_t preprocess(PreCache* c, const uint8_t* pixels, const miclip_image_desc* descs, int B,
                       int n, int out_kind, void* out, hipStream_t s, char* err, int errlen);
+// The train transform: per image augs[i] (HOST array) picks the geometry, the
+// mirror and the rotation; tables and scratch are per call, owned by the cache.
+hipError_t preprocess_aug(PreCache* c, const uint8_t* pixels, const miclip_image_desc* descs,
+                          const miclip_aug_desc* augs, int B, int n, int out_kind, void* out,
+                          hipStream_t s, char* err, int errlen);
 
 }  // namespace miclip

@@ -22,6 +22,17 @@
 //     accumulated with v_mad_i32_i24 (|coefficient| < 2^23, pixel < 2^8).
 // HBM-bound in principle (each byte of the crop window is read about once;
 // L1/L2 absorb the overlap of neighbouring taps).
+//
+// The train transform (data/clip_transforms.py:36-49,
+// `preprocess_aug`) runs on the same resampler with host-drawn parameters:
+//   * `aug_tables_kernel` writes every image's tables in one launch into a
+//     per-call arena: RandomResizedCrop gives each image its own box, so the
+//     box is resampled as an image of its own (crop, then resize) and nothing
+//     is worth caching; BottomSquareCrop is the identity resize of its box;
+//   * `preprocess_kernel<., true>` mirrors the store column for the flip;
+//   * `rotate_kernel` gathers RandomRotation's nearest-neighbour source pixel
+//     with Pillow's 16.16 fixed-point affine rule from the resized uint8 image
+//     (a second pass: the gather crosses the bands).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -157,10 +168,24 @@ __device__ __forceinline__ int byte_of(uint32_t w, int i) {
   return (int)__builtin_amdgcn_ubfe(w, 8 * i, 8);
 }
 
-template <int OUT>  // 0: float32 normalised planar [B,3,n,n]; 1: uint8 crop [B,n,n,3]
+// One image's augmentation (device copy): what aug_tables_kernel resamples
+// (in -> out size and the first output index of each axis, tap counts), the
+// mirror of the resampled image and the rotation's 16.16 output -> source map.
+struct AugImage {
+  int32_t in_w, out_w, left, KH;
+  int32_t in_h, out_h, top, KV;
+  int32_t flip, rotate;
+  int32_t a[6];
+};
+static_assert(sizeof(AugImage) == 64, "AugImage layout");
+
+// OUT 0: float32 normalised planar [B,3,n,n]; 1: uint8 crop [B,n,n,3].
+// AUG: `aug[b].flip` mirrors the store column (the resampled image is flipped).
+template <int OUT, bool AUG>
 __global__ __launch_bounds__(kThreads) void preprocess_kernel(
     const uint8_t* __restrict__ pix, const PreImage* __restrict__ imgs,
-    const int* __restrict__ tabs, int n, int KH, int KV, void* __restrict__ out) {
+    const int* __restrict__ tabs, int n, int KH, int KV, void* __restrict__ out,
+    const AugImage* __restrict__ aug) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   int* kh = (int*)smem;                      // [n][KH], KH % 16 == 0, zero-padded
   int* khb = kh + n * KH;                    // [n][2] xmin, count
@@ -178,6 +203,7 @@ __global__ __launch_bounds__(kThreads) void preprocess_kernel(
   const int* vb = hk + n * KHg;
   const int* vk = vb + 2 * n;
   const int nrows = n - i0 < kBand ? n - i0 : kBand;
+  const bool flip = AUG && aug[b].flip != 0;
 
   for (int e = tid; e < n * KH; e += kThreads) {
     const int j = e / KH, t = e - j * KH;
@@ -319,8 +345,9 @@ __global__ __launch_bounds__(kThreads) void preprocess_kernel(
         u[0] = u[1] = u[2] = clip8(a0);   // convert("RGB") of an 'L' image
       }
       const int orow = i0 + i;
+      const int ocol = AUG && flip ? n - 1 - j : j;
       if (OUT == 1) {
-        uint8_t* o = (uint8_t*)out + (((size_t)b * n + orow) * n + j) * 3;
+        uint8_t* o = (uint8_t*)out + (((size_t)b * n + orow) * n + ocol) * 3;
         o[0] = (uint8_t)u[0];
         o[1] = (uint8_t)u[1];
         o[2] = (uint8_t)u[2];
@@ -328,7 +355,7 @@ __global__ __launch_bounds__(kThreads) void preprocess_kernel(
         // float32(python float) constants, as torch builds the Normalize tensors
         const float mean[3] = {(float)0.48145466, (float)0.4578275, (float)0.40821073};
         const float stdv[3] = {(float)0.26862954, (float)0.26130258, (float)0.27577711};
-        float* o = (float*)out + (size_t)b * 3 * n * n + (size_t)orow * n + j;
+        float* o = (float*)out + (size_t)b * 3 * n * n + (size_t)orow * n + ocol;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
           const float x = (float)u[c] / 255.0f;
@@ -338,6 +365,76 @@ __global__ __launch_bounds__(kThreads) void preprocess_kernel(
     }
     __syncthreads();
     s0 = s1;
+  }
+}
+
+// Coefficient tables of a whole augmented batch in one launch: block (b, .)
+// writes image b's table (pre_tables_kernel's layout and arithmetic) at
+// imgs[b].tab of the per-call arena. Every image has its own box, so nothing
+// here is worth caching.
+__global__ __launch_bounds__(256) void aug_tables_kernel(const PreImage* __restrict__ imgs,
+                                                         const AugImage* __restrict__ aug, int n,
+                                                         int* __restrict__ arena) {
+  const AugImage a = aug[blockIdx.x];
+  int* tab = arena + imgs[blockIdx.x].tab;
+  int* hb = tab + 8;
+  int* hk = hb + 2 * n;
+  int* vb = hk + n * a.KH;
+  int* vk = vb + 2 * n;
+  const int i = blockIdx.y * 256 + threadIdx.x;
+  if (i == 0) {
+    tab[0] = a.KH;
+    tab[1] = a.KV;
+    for (int e = 2; e < 8; ++e) tab[e] = 0;
+  }
+  if (i < n)
+    coeffs(a.in_w, a.out_w, a.left + i, a.KH, hk + i * a.KH, hb + 2 * i);
+  else if (i < 2 * n)
+    coeffs(a.in_h, a.out_h, a.top + (i - n), a.KV, vk + (i - n) * a.KV, vb + 2 * (i - n));
+}
+
+// RandomRotation(30) = Image.rotate(NEAREST, expand=False, fillcolor=0) of the
+// resized uint8 [B,n,n,3] image `src`: Geometry.c affine_fixed's gather
+//   xin = (a2 + y*a1 + x*a0) >> 16, yin = (a5 + y*a4 + x*a3) >> 16
+// with the sums in wrapping 32-bit arithmetic (unsigned here), 0 outside the
+// image. One thread per output pixel; images of the batch that are not rotated
+// are copied. Output as preprocess_kernel's.
+template <int OUT>
+__global__ __launch_bounds__(256) void rotate_kernel(const uint8_t* __restrict__ src,
+                                                     const AugImage* __restrict__ aug, int n,
+                                                     void* __restrict__ out) {
+  const int b = blockIdx.x;
+  const int p = blockIdx.y * 256 + threadIdx.x;
+  if (p >= n * n) return;
+  const int y = p / n, x = p - y * n;
+  const AugImage a = aug[b];
+  int xin = x, yin = y;
+  if (a.rotate) {
+    const uint32_t ux = (uint32_t)x, uy = (uint32_t)y;
+    xin = (int)((uint32_t)a.a[2] + uy * (uint32_t)a.a[1] + ux * (uint32_t)a.a[0]) >> 16;
+    yin = (int)((uint32_t)a.a[5] + uy * (uint32_t)a.a[4] + ux * (uint32_t)a.a[3]) >> 16;
+  }
+  int u[3] = {0, 0, 0};
+  if (xin >= 0 && xin < n && yin >= 0 && yin < n) {
+    const uint8_t* q = src + (((size_t)b * n + yin) * n + xin) * 3;
+    u[0] = q[0];
+    u[1] = q[1];
+    u[2] = q[2];
+  }
+  if (OUT == 1) {
+    uint8_t* o = (uint8_t*)out + ((size_t)b * n * n + p) * 3;
+    o[0] = (uint8_t)u[0];
+    o[1] = (uint8_t)u[1];
+    o[2] = (uint8_t)u[2];
+  } else {
+    const float mean[3] = {(float)0.48145466, (float)0.4578275, (float)0.40821073};
+    const float stdv[3] = {(float)0.26862954, (float)0.26130258, (float)0.27577711};
+    float* o = (float*)out + (size_t)b * 3 * n * n + p;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float v = (float)u[c] / 255.0f;
+      o[(size_t)c * n * n] = (v - mean[c]) / stdv[c];
+    }
   }
 }
 
@@ -361,6 +458,14 @@ struct PreCache {
   int img_cap = 0;
   hipEvent_t copied = nullptr;        // last image-array upload done
   bool copy_pending = false;
+  // preprocess_aug: per-call state, reused from call to call (stream-ordered)
+  AugImage* dev_aug = nullptr;
+  AugImage* host_aug = nullptr;       // pinned
+  int aug_cap = 0;
+  int* arena = nullptr;               // the batch's coefficient tables
+  size_t arena_cap = 0;               // ints
+  uint8_t* rot = nullptr;             // resized uint8 [B,n,n,3], input of the rotation
+  size_t rot_cap = 0;                 // bytes
 };
 
 PreCache* pre_cache_create() { return new PreCache(); }
@@ -371,20 +476,20 @@ void pre_cache_destroy(PreCache* c) {
   if (c->tabs) (void)hipFree(c->tabs);
   if (c->dev_imgs) (void)hipFree(c->dev_imgs);
   if (c->host_imgs) (void)hipHostFree(c->host_imgs);
+  if (c->dev_aug) (void)hipFree(c->dev_aug);
+  if (c->host_aug) (void)hipHostFree(c->host_aug);
+  if (c->arena) (void)hipFree(c->arena);
+  if (c->rot) (void)hipFree(c->rot);
   if (c->copied) (void)hipEventDestroy(c->copied);
   delete c;
 }
 
-hipError_t preprocess(PreCache* c, const uint8_t* pixels, const miclip_image_desc* descs, int B,
-                      int n, int out_kind, void* out, hipStream_t s, char* err, int errlen) {
-  if (!c || B < 1 || n < 1 || n > 1024 || (out_kind != 0 && out_kind != 1)) {
-    snprintf(err, errlen, "preprocess: bad batch %d / resolution %d / output kind %d", B, n,
-             out_kind);
-    return hipErrorInvalidValue;
-  }
+namespace {
+
+// Image-array buffers for a batch of B, and the pinned staging free to write
+// (the previous call's upload has left it).
+hipError_t reserve_images(PreCache* c, int B, hipStream_t s) {
   hipError_t e;
-  // validate, find or build each image's geometry table
-  int KH = 4, KV = 1;
   if (B > c->img_cap) {
     if (c->copy_pending && (e = hipEventSynchronize(c->copied)) != hipSuccess) return e;
     c->copy_pending = false;
@@ -403,12 +508,51 @@ hipError_t preprocess(PreCache* c, const uint8_t* pixels, const miclip_image_des
     return e;
   if (c->copy_pending && (e = hipEventSynchronize(c->copied)) != hipSuccess) return e;
   c->copy_pending = false;
+  return hipSuccess;
+}
+
+// Grows a handle-owned device buffer that earlier launches on `s` may still use.
+template <typename T>
+hipError_t grow_device(T** p, size_t* cap, size_t need, hipStream_t s) {
+  if (need <= *cap) return hipSuccess;
+  hipError_t e;
+  if (*p) {
+    if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
+    (void)hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+  }
+  size_t n = *cap ? *cap : 1;
+  while (n < need) n *= 2;
+  if ((e = hipMalloc(p, n * sizeof(T))) != hipSuccess) return e;
+  *cap = n;
+  return hipSuccess;
+}
+
+bool valid_desc(const miclip_image_desc& d, int64_t* stride, int64_t* extent) {
+  *stride = d.row_stride ? d.row_stride : (int64_t)d.width * d.channels;
+  *extent = (int64_t)(d.height - 1) * *stride + (int64_t)d.width * d.channels;
+  return !(d.height < 1 || d.width < 1 || (d.channels != 1 && d.channels != 3) || d.offset < 0 ||
+           *stride < (int64_t)d.width * d.channels || *extent >= (1ll << 32) - 16);
+}
+
+}  // namespace
+
+hipError_t preprocess(PreCache* c, const uint8_t* pixels, const miclip_image_desc* descs, int B,
+                      int n, int out_kind, void* out, hipStream_t s, char* err, int errlen) {
+  if (!c || B < 1 || n < 1 || n > 1024 || (out_kind != 0 && out_kind != 1)) {
+    snprintf(err, errlen, "preprocess: bad batch %d / resolution %d / output kind %d", B, n,
+             out_kind);
+    return hipErrorInvalidValue;
+  }
+  hipError_t e;
+  // validate, find or build each image's geometry table
+  int KH = 4, KV = 1;
+  if ((e = reserve_images(c, B, s)) != hipSuccess) return e;
   for (int i = 0; i < B; ++i) {
     const miclip_image_desc& d = descs[i];
-    const int64_t stride = d.row_stride ? d.row_stride : (int64_t)d.width * d.channels;
-    const int64_t extent = (int64_t)(d.height - 1) * stride + (int64_t)d.width * d.channels;
-    if (d.height < 1 || d.width < 1 || (d.channels != 1 && d.channels != 3) || d.offset < 0 ||
-        stride < (int64_t)d.width * d.channels || extent >= (1ll << 32) - 16) {
+    int64_t stride, extent;
+    if (!valid_desc(d, &stride, &extent)) {
       snprintf(err, errlen, "preprocess: image %d has an invalid descriptor (%dx%dx%d, stride %d)",
                i, d.height, d.width, d.channels, d.row_stride);
       return hipErrorInvalidValue;
@@ -473,15 +617,160 @@ hipError_t preprocess(PreCache* c, const uint8_t* pixels, const miclip_image_des
   c->copy_pending = true;
   const dim3 grid(B, (n + kBand - 1) / kBand);
   if (out_kind == 0) {
-    static const hipError_t a0 = set_lds_attr((const void*)preprocess_kernel<0>);
+    static const hipError_t a0 = set_lds_attr((const void*)preprocess_kernel<0, false>);
     if (a0 != hipSuccess) return a0;
-    hipLaunchKernelGGL(preprocess_kernel<0>, grid, dim3(kThreads), lds, s, pixels, c->dev_imgs,
-                       c->tabs, n, KH, KV, out);
+    hipLaunchKernelGGL((preprocess_kernel<0, false>), grid, dim3(kThreads), lds, s, pixels,
+                       c->dev_imgs, c->tabs, n, KH, KV, out, (const AugImage*)nullptr);
   } else {
-    static const hipError_t a1 = set_lds_attr((const void*)preprocess_kernel<1>);
+    static const hipError_t a1 = set_lds_attr((const void*)preprocess_kernel<1, false>);
     if (a1 != hipSuccess) return a1;
-    hipLaunchKernelGGL(preprocess_kernel<1>, grid, dim3(kThreads), lds, s, pixels, c->dev_imgs,
-                       c->tabs, n, KH, KV, out);
+    hipLaunchKernelGGL((preprocess_kernel<1, false>), grid, dim3(kThreads), lds, s, pixels,
+                       c->dev_imgs, c->tabs, n, KH, KV, out, (const AugImage*)nullptr);
+  }
+  return hipGetLastError();
+}
+
+// The reference's train transform (data/clip_transforms.py:36-49) with host-drawn
+// parameters: per image a geometry (today's resize + centre crop, a box stretched
+// to n x n = RandomResizedCrop, or a plain n x n crop = BottomSquareCrop), a
+// mirror and a rotation. STRETCH and CROP are crop-then-resize, so the kernel
+// sees the box as an image of its own: offset, extent and tables of the
+// sub-rectangle (a CROP's tables are the identity, an exact copy). One tables
+// launch and one resample launch per batch; a batch with a rotated image resamples
+// into uint8 scratch and a gather launch writes the output.
+hipError_t preprocess_aug(PreCache* c, const uint8_t* pixels, const miclip_image_desc* descs,
+                          const miclip_aug_desc* augs, int B, int n, int out_kind, void* out,
+                          hipStream_t s, char* err, int errlen) {
+  if (!c || B < 1 || n < 1 || n > 1024 || (out_kind != 0 && out_kind != 1)) {
+    snprintf(err, errlen, "preprocess_aug: bad batch %d / resolution %d / output kind %d", B, n,
+             out_kind);
+    return hipErrorInvalidValue;
+  }
+  hipError_t e;
+  if ((e = reserve_images(c, B, s)) != hipSuccess) return e;
+  if (B > c->aug_cap) {
+    if (c->dev_aug && (e = hipStreamSynchronize(s)) != hipSuccess) return e;
+    if (c->dev_aug) (void)hipFree(c->dev_aug);
+    if (c->host_aug) (void)hipHostFree(c->host_aug);
+    c->dev_aug = nullptr;
+    c->host_aug = nullptr;
+    c->aug_cap = 0;
+    const int cap = B < 256 ? 256 : B;
+    if ((e = hipMalloc(&c->dev_aug, sizeof(AugImage) * cap)) != hipSuccess) return e;
+    if ((e = hipHostMalloc(&c->host_aug, sizeof(AugImage) * cap)) != hipSuccess) return e;
+    c->aug_cap = cap;
+  }
+  int KH = 4, KV = 1;
+  bool any_rot = false;
+  size_t ints = 0;
+  for (int i = 0; i < B; ++i) {
+    const miclip_image_desc& d = descs[i];
+    const miclip_aug_desc& g = augs[i];
+    int64_t stride, extent;
+    if (!valid_desc(d, &stride, &extent)) {
+      snprintf(err, errlen,
+               "preprocess_aug: image %d has an invalid descriptor (%dx%dx%d, stride %d)", i,
+               d.height, d.width, d.channels, d.row_stride);
+      return hipErrorInvalidValue;
+    }
+    PreImage& p = c->host_imgs[i];
+    AugImage& a = c->host_aug[i];
+    p.offset = d.offset;
+    p.H = d.height;
+    p.W = d.width;
+    if (g.mode == MICLIP_AUG_RESIZE_CENTER) {
+      const Geo q = geometry(d.height, d.width, n);
+      a.in_w = d.width, a.out_w = q.nw, a.left = q.left;
+      a.in_h = d.height, a.out_h = q.nh, a.top = q.top;
+    } else if (g.mode == MICLIP_AUG_STRETCH || g.mode == MICLIP_AUG_CROP) {
+      if (g.top < 0 || g.left < 0 || g.height < 1 || g.width < 1 ||
+          (int64_t)g.top + g.height > d.height || (int64_t)g.left + g.width > d.width) {
+        snprintf(err, errlen, "preprocess_aug: image %d: box (top %d, left %d, %dx%d) leaves the "
+                 "%dx%d image", i, g.top, g.left, g.height, g.width, d.height, d.width);
+        return hipErrorInvalidValue;
+      }
+      if (g.mode == MICLIP_AUG_CROP && (g.height != n || g.width != n)) {
+        snprintf(err, errlen, "preprocess_aug: image %d: a CROP box is %dx%d, not %dx%d", i,
+                 g.height, g.width, n, n);
+        return hipErrorInvalidValue;
+      }
+      p.offset += (int64_t)g.top * stride + (int64_t)g.left * d.channels;
+      p.H = g.height;
+      p.W = g.width;
+      extent = (int64_t)(g.height - 1) * stride + (int64_t)g.width * d.channels;
+      a.in_w = g.width, a.out_w = n, a.left = 0;
+      a.in_h = g.height, a.out_h = n, a.top = 0;
+    } else {
+      snprintf(err, errlen, "preprocess_aug: image %d: unknown mode %d", i, g.mode);
+      return hipErrorInvalidValue;
+    }
+    a.KH = ksize_for(a.in_w, a.out_w);
+    a.KV = ksize_for(a.in_h, a.out_h);
+    // a single crop row's vertical taps must fit the LDS staging area
+    if (a.KH > kMaxTaps || a.KV > kMaxTaps || a.KV > kTmpBytes / (n * 3)) {
+      snprintf(err, errlen,
+               "preprocess_aug: image %d (%dx%d) downscales too far for resolution %d (taps %d x "
+               "%d, max %d)", i, a.in_h, a.in_w, n, a.KH, a.KV, kMaxTaps);
+      return hipErrorInvalidValue;
+    }
+    a.flip = g.flip != 0;
+    a.rotate = g.rotate != 0;
+    for (int k = 0; k < 6; ++k) a.a[k] = g.affine[k];
+    any_rot |= a.rotate != 0;
+    p.extent = (uint32_t)extent;
+    p.C = d.channels;
+    p.stride = (int32_t)stride;
+    p.tab = (int32_t)ints;
+    ints += (size_t)table_ints(n, a.KH, a.KV);
+    if (ints >= ((size_t)1 << 31)) {
+      snprintf(err, errlen, "preprocess_aug: the coefficient tables of %d images exceed 2^31 "
+               "entries", B);
+      return hipErrorInvalidValue;
+    }
+    KH = a.KH > KH ? a.KH : KH;
+    KV = a.KV > KV ? a.KV : KV;
+  }
+  KH = (KH + 15) & ~15;
+  const size_t lds = (size_t)(n * KH + 2 * n + kBand * KV + 2 * kBand) * 4 + kTmpBytes;
+  if (lds > 160 * 1024) {
+    snprintf(err, errlen, "preprocess_aug: LDS need %zu B exceeds 160 KiB", lds);
+    return hipErrorInvalidValue;
+  }
+  if ((e = grow_device(&c->arena, &c->arena_cap, ints, s)) != hipSuccess) return e;
+  if (any_rot &&
+      (e = grow_device(&c->rot, &c->rot_cap, (size_t)B * n * n * 3, s)) != hipSuccess)
+    return e;
+  if ((e = hipMemcpyAsync(c->dev_imgs, c->host_imgs, sizeof(PreImage) * B, hipMemcpyHostToDevice,
+                          s)) != hipSuccess)
+    return e;
+  if ((e = hipMemcpyAsync(c->dev_aug, c->host_aug, sizeof(AugImage) * B, hipMemcpyHostToDevice,
+                          s)) != hipSuccess)
+    return e;
+  if ((e = hipEventRecord(c->copied, s)) != hipSuccess) return e;
+  c->copy_pending = true;
+  hipLaunchKernelGGL(aug_tables_kernel, dim3(B, (2 * n + 255) / 256), dim3(256), 0, s,
+                     c->dev_imgs, c->dev_aug, n, c->arena);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  const dim3 grid(B, (n + kBand - 1) / kBand);
+  if (any_rot || out_kind == 1) {
+    static const hipError_t a1 = set_lds_attr((const void*)preprocess_kernel<1, true>);
+    if (a1 != hipSuccess) return a1;
+    hipLaunchKernelGGL((preprocess_kernel<1, true>), grid, dim3(kThreads), lds, s, pixels,
+                       c->dev_imgs, c->arena, n, KH, KV, any_rot ? (void*)c->rot : out,
+                       c->dev_aug);
+  } else {
+    static const hipError_t a0 = set_lds_attr((const void*)preprocess_kernel<0, true>);
+    if (a0 != hipSuccess) return a0;
+    hipLaunchKernelGGL((preprocess_kernel<0, true>), grid, dim3(kThreads), lds, s, pixels,
+                       c->dev_imgs, c->arena, n, KH, KV, out, c->dev_aug);
+  }
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  if (any_rot) {
+    const dim3 rgrid(B, (n * n + 255) / 256);
+    if (out_kind == 0)
+      hipLaunchKernelGGL(rotate_kernel<0>, rgrid, dim3(256), 0, s, c->rot, c->dev_aug, n, out);
+    else
+      hipLaunchKernelGGL(rotate_kernel<1>, rgrid, dim3(256), 0, s, c->rot, c->dev_aug, n, out);
   }
   return hipGetLastError();
 }

@@ -13,7 +13,8 @@ import warnings
 
 import torch
 
-from . import evaluation
+from . import augment, evaluation
+from .augment import build_clip_transforms
 from .configs import (MODEL_CONFIGS, OPEN_CLIP_MODELS, CLIPConfig, available_models,
                       config_from_state_dict)
 from .evaluation import (ClassificationTracker, Evaluator, L2MetricsAccumulator,
@@ -26,7 +27,8 @@ from .weights import generate_state_dict, synthetic_images
 __all__ = ["available_models", "load", "tokenize", "build_model", "CLIP", "CLIPConfig",
            "MODEL_CONFIGS", "SeededWeightsWarning", "evaluation", "run_validation",
            "evaluate_features", "Evaluator", "L2MetricsAccumulator", "ClassificationTracker",
-           "aggregate_logits_to_l2", "map_l3_targets_to_l2"]
+           "aggregate_logits_to_l2", "map_l3_targets_to_l2", "augment",
+           "build_clip_transforms"]
 
 
 class SeededWeightsWarning(UserWarning):

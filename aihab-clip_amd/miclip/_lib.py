@@ -43,7 +43,7 @@ EXPORTS = (
     "miclip_model_destroy", "miclip_last_error", "miclip_abi_version",
     "miclip_model_bytes", "miclip_model_flags", "miclip_model_set_option", "miclip_set_gemm_variant", "miclip_set_profiling", "miclip_profile_read", "miclip_set_splits", "miclip_image_splits",
     "miclip_op_gemm", "miclip_op_gemm_splitk", "miclip_op_ln_stats", "miclip_op_ln_fold", "miclip_op_gemm_ln",
-    "miclip_op_layernorm", "miclip_op_attention", "miclip_op_attention_q0", "miclip_op_im2col", "miclip_preprocess",
+    "miclip_op_layernorm", "miclip_op_attention", "miclip_op_attention_q0", "miclip_op_im2col", "miclip_preprocess", "miclip_preprocess_aug",
     "miclip_row_norms", "miclip_class_centroids", "miclip_proto_scores",
     "miclip_kmeans_scratch_bytes", "miclip_kmeans_seed", "miclip_kmeans_lloyd",
     "miclip_prolip_grad", "miclip_prolip_adam",
@@ -53,6 +53,10 @@ EXPORTS = (
 
 MICLIP_PRE_F32 = 0
 MICLIP_PRE_U8 = 1
+# miclip_aug_desc.mode (include/miclip.h MICLIP_AUG_*)
+MICLIP_AUG_RESIZE_CENTER = 0
+MICLIP_AUG_STRETCH = 1
+MICLIP_AUG_CROP = 2
 # miclip_eval_batch l2_mode / flags (include/miclip.h MICLIP_EVAL_*)
 MICLIP_EVAL_L2_NONE = 0
 MICLIP_EVAL_L2_ARGMAX = 1
@@ -82,6 +86,11 @@ class MiclipKernelStat(ctypes.Structure):
 class MiclipImageDesc(ctypes.Structure):
     _fields_ = [("offset", ctypes.c_int64), ("height", ctypes.c_int32), ("width", ctypes.c_int32),
                 ("channels", ctypes.c_int32), ("row_stride", ctypes.c_int32)]
+
+
+class MiclipAugDesc(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("mode", "top", "left", "height", "width", "flip",
+                                               "rotate")] + [("affine", ctypes.c_int32 * 6)]
 
 
 class MiclipError(RuntimeError):
@@ -144,6 +153,8 @@ def load_library(path: str = None):
         "miclip_op_layernorm_mx": ([vp, i32, vp, vp, vp, vp, i32, i32, vp], ctypes.c_int),
         "miclip_preprocess": ([vp, vp, ctypes.POINTER(MiclipImageDesc), i32, vp, i32, vp],
                               ctypes.c_int),
+        "miclip_preprocess_aug": ([vp, vp, ctypes.POINTER(MiclipImageDesc),
+                                   ctypes.POINTER(MiclipAugDesc), i32, vp, i32, vp], ctypes.c_int),
         "miclip_row_norms": ([vp, i32, i32, vp, f32, vp, vp], ctypes.c_int),
         "miclip_class_centroids": ([vp, vp, vp, i32, i32, f32, vp, vp, vp], ctypes.c_int),
         "miclip_proto_scores": ([vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp],

@@ -13,7 +13,9 @@ plus what the reference does not have:
     memory on a side stream instead of a synchronous
     `.to("cpu")` per batch;
   * prepare_images: loaders may yield decoded uint8 images, transformed on
-    the GPU by `CLIP.preprocess_images` (SURVEY §8f row 1);
+    the GPU by `CLIP.preprocess_images`, for the training
+    cache with the reference's train augmentations (SURVEY §8f rows 14, 15:
+    cfg data.preprocessing, one parameter set per (seed, view, row));
 and the multi-GPU variant:
   * shard_range / sharded_encode / compute_image_features_sharded: each rank
     encodes a contiguous slice of the image batch and the L2-normalised (or
@@ -173,29 +175,49 @@ def is_raw_batch(images) -> bool:
         getattr(images[0], "dtype", None) in (np.uint8, torch.uint8)
 
 
-def prepare_images(model, images, device):
+def raw_sizes(images):
+    """(H, W) of every image of a decoded uint8 batch (is_raw_batch)."""
+    if isinstance(images, torch.Tensor):
+        return [(int(images.shape[1]), int(images.shape[2]))] * int(images.shape[0])
+    return [(int(im.shape[0]), int(im.shape[1])) for im in images]
+
+
+def prepare_images(model, images, device, augment=None):
     """Model-ready float32 [B,3,R,R] on `device`: decoded uint8 batches go through the
-    on-device transform (`CLIP.preprocess_images`); tensors that
-    the loader already transformed (the reference's path) are moved as they are."""
+    on-device transform (`CLIP.preprocess_images`), with the train
+    augmentation parameters `augment` (one `augment.AugParams` per image) when given;
+    tensors that the loader already transformed (the reference's path) are moved as
+    they are."""
     if is_raw_batch(images):
         if not hasattr(model, "preprocess_images"):
             raise ValueError("uint8 image batches need a miclip model (on-device preprocessing)")
-        return model.preprocess_images(images)
+        if augment is None:
+            return model.preprocess_images(images)
+        return model.preprocess_images(images, augment=augment)
     return images.to(device, non_blocking=True)
 
 
 @torch.no_grad()
-def compute_image_features(clip_model, loader, to_cpu: bool = False, out_dtype=None):
+def compute_image_features(clip_model, loader, to_cpu: bool = False, out_dtype=None,
+                           augment=None):
     """Pre-projection features and labels of every batch (methods/utils.py:142-173).
 
     With to_cpu the per-batch host copies are asynchronous (AsyncHostSink);
     loaders may also yield decoded uint8 images (prepare_images). out_dtype
     (torch.float16 / bfloat16) rounds the features in the encode's own head
-    launch sequence (fp32 by default)."""
+    launch sequence (fp32 by default). augment(sizes, first_row) -> one
+    `augment.AugParams` per image gives the train augmentations of a raw uint8
+    batch whose first image is row `first_row` of the pass (sizes: its (H, W)
+    list); batches of transformed tensors are left alone."""
     device = _model_device(clip_model)
     feats, labels = ([], []) if not to_cpu else (AsyncHostSink(), [])
+    row = 0
     for images, target in loader:
-        x = _encode(clip_model, prepare_images(clip_model, images, device), out_dtype)
+        params = None
+        if augment is not None and is_raw_batch(images):
+            params = augment(raw_sizes(images), row)
+        row += len(images)
+        x = _encode(clip_model, prepare_images(clip_model, images, device, params), out_dtype)
         if to_cpu:
             feats.push(x)
             labels.append(target.detach().to("cpu"))
@@ -295,13 +317,35 @@ def cache_openclip_embeddings(cfg: dict, model, loader, split: str = "test",
     return cache_dir
 
 
+def _view_sampler(cfg, clip_model, view: int):
+    """augment callable of view `view` from cfg data.preprocessing, or None."""
+    pre = (cfg.get("data", {}) or {}).get("preprocessing") if hasattr(cfg, "get") else None
+    if not pre or not hasattr(clip_model, "preprocess_images"):
+        return None
+    from .augment import sample_params
+    R = int(clip_model.config.image_resolution)
+    if int(pre.get("resolution", R)) != R:
+        raise ValueError(f"data.preprocessing.resolution {pre.get('resolution')} is not the "
+                         f"model's input resolution {R}")
+    aug = pre.get("augmentations", {}) or {}
+    seed = int(cfg.get("seed", 1) or 1)
+    return lambda sizes, row: sample_params(sizes, aug, R, seed, view, row)
+
+
 @torch.no_grad()
 def cache_preprojection_features(cfg, clip_bundle: dict, dl_tr, info: dict):
     """f{v}.pth per augmentation view + label.pth (aihab_utils/feature_cache.py:189-250).
 
     The features are fp16 like the reference's (its clip.load(..., device="cuda")
     model is fp16, so compute_image_features returns fp16, :211); cfg
-    "cache_dtype" "fp32" / "bf16" picks another element type."""
+    "cache_dtype" "fp32" / "bf16" picks another element type.
+
+    With cfg["data"]["preprocessing"] (the reference's layout: `resolution`,
+    `augmentations`) and a loader of decoded uint8 images, view v is the
+    reference's train transform on the GPU: row i of the pass gets the
+    parameters `augment.sample_params` draws for (cfg["seed"], v, i), whatever
+    the batch size. Without that key, or for loaders that yield transformed
+    tensors (the reference's own path), every pass is what the loader yields."""
     clip_model = clip_bundle["clip_model"]
     cache_dir = _feature_cache_dir(cfg)
     num_views = int(cfg.get("aug_views", 1) or 1)
@@ -312,7 +356,8 @@ def cache_preprojection_features(cfg, clip_bundle: dict, dl_tr, info: dict):
     clip_model.eval()
     for v in range(num_views):
         feats_t, labels_t = compute_image_features(clip_model, dl_tr, to_cpu=True,
-                                                   out_dtype=out_dtype)
+                                                   out_dtype=out_dtype,
+                                                   augment=_view_sampler(cfg, clip_model, v))
         fpath = cache_dir / f"f{v}.pth"
         fpath.parent.mkdir(parents=True, exist_ok=True)
         torch.save(feats_t, fpath)

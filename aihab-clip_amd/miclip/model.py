@@ -360,7 +360,7 @@ class CLIP(nn.Module):
         return out
 
     @torch.no_grad()
-    def preprocess_images(self, images, uint8=False, out=None):
+    def preprocess_images(self, images, uint8=False, out=None, augment=None):
         """On-device `_transform(R)` (clip/clip.py:74-81) of decoded uint8 images.
 
         images: a uint8 tensor [B, H, W, C] (any device) or a list of uint8
@@ -368,6 +368,12 @@ class CLIP(nn.Module):
         Returns float32 [B, 3, R, R] (ToTensor + Normalize), or with uint8=True
         the resized + center-cropped pixels uint8 [B, R, R, 3]; bit-exact with
         Pillow's bicubic resize + torchvision's crop.
+
+        augment: one `miclip.augment.AugParams` per image (`sample_params`) selects
+        the reference's train transform (data/clip_transforms.py:36-49): the box of
+        RandomResizedCrop / BottomSquareCrop, the flip and the rotation, with the
+        same outputs, bit-exact with Pillow (`augment.apply_params`). None is the
+        test transform.
         """
         h = self._require()
         R = self.config.image_resolution
@@ -378,6 +384,7 @@ class CLIP(nn.Module):
             B, H, W, C = buf.shape
             descs = (_lib.MiclipImageDesc * max(B, 1))(
                 *[_lib.MiclipImageDesc(i * H * W * C, H, W, C, 0) for i in range(B)])
+            sizes = [(H, W)] * B
         else:
             arrs = []
             for im in images:
@@ -397,6 +404,8 @@ class CLIP(nn.Module):
             descs = (_lib.MiclipImageDesc * max(B, 1))(
                 *[_lib.MiclipImageDesc(int(offs[i]), a.shape[0], a.shape[1], a.shape[2], 0)
                   for i, a in enumerate(arrs)])
+            sizes = [a.shape[:2] for a in arrs]
+        augs = self._aug_descs(augment, sizes, R) if augment is not None else None
         shape = (B, R, R, 3) if uint8 else (B, 3, R, R)
         dt = torch.uint8 if uint8 else torch.float32
         if out is None:
@@ -405,14 +414,41 @@ class CLIP(nn.Module):
             raise ValueError(f"out must be a contiguous {dt} tensor of shape {shape}")
         if B == 0:
             return out
+        kind = _lib.MICLIP_PRE_U8 if uint8 else _lib.MICLIP_PRE_F32
         with torch.cuda.device(self.device):
-            _lib.check(h.lib.miclip_preprocess(h.ptr, buf.data_ptr(), descs, B, out.data_ptr(),
-                                               _lib.MICLIP_PRE_U8 if uint8 else _lib.MICLIP_PRE_F32,
-                                               _lib.stream_handle(self.device)),
-                       "miclip_preprocess")
+            if augs is None:
+                _lib.check(h.lib.miclip_preprocess(h.ptr, buf.data_ptr(), descs, B, out.data_ptr(),
+                                                   kind, _lib.stream_handle(self.device)),
+                           "miclip_preprocess")
+            else:
+                _lib.check(h.lib.miclip_preprocess_aug(h.ptr, buf.data_ptr(), descs, augs, B,
+                                                       out.data_ptr(), kind,
+                                                       _lib.stream_handle(self.device)),
+                           "miclip_preprocess_aug")
         if buf.is_cuda:
             buf.record_stream(torch.cuda.current_stream(self.device))
         return out
+
+    @staticmethod
+    def _aug_descs(augment, sizes, R):
+        """miclip_aug_desc array of `augment` (AugParams per image)."""
+        from . import augment as A
+        augment = list(augment)
+        if len(augment) != len(sizes):
+            raise ValueError(f"augment has {len(augment)} entries for {len(sizes)} images")
+        if not sizes:
+            return (_lib.MiclipAugDesc * 1)()
+        rows, none = [], (0,) * 6
+        for p, (H, W) in zip(augment, sizes):
+            if p.mode == A.CROP and (R > W or R > H):
+                raise ValueError(A.CROP_ERROR)      # BottomSquareCrop's own error
+            rows.append((p.mode, p.top, p.left, p.height, p.width, bool(p.flip),
+                         p.angle is not None)
+                        + (none if p.angle is None else A.rotation_affine(float(p.angle), R, R)))
+        arr = np.asarray(rows, dtype=np.int64)      # one row = one miclip_aug_desc
+        if arr.min() < -2 ** 31 or arr.max() >= 2 ** 31:
+            raise ValueError("augmentation parameters exceed 32 bits")
+        return (_lib.MiclipAugDesc * len(rows)).from_buffer(np.ascontiguousarray(arr, np.int32))
 
     @torch.no_grad()
     def encode_text(self, text, normalize=False):

@@ -191,6 +191,40 @@ enum miclip_pre_out {
 int miclip_preprocess(miclip_model* m, const uint8_t* pixels, const miclip_image_desc* descs,
                       int32_t B, void* out, int32_t out_kind, void* stream);
 
+enum miclip_aug_mode {
+  MICLIP_AUG_RESIZE_CENTER = 0, /* Resize(R) of the short side + CenterCrop(R), as miclip_preprocess */
+  MICLIP_AUG_STRETCH = 1,       /* crop the box, then resize it to R x R (RandomResizedCrop) */
+  MICLIP_AUG_CROP = 2           /* crop the R x R box (BottomSquareCrop) */
+};
+
+/* One image's train-transform parameters, drawn by the caller. */
+typedef struct miclip_aug_desc {
+  int32_t mode;                     /* miclip_aug_mode */
+  int32_t top, left, height, width; /* box inside the image: STRETCH, CROP */
+  int32_t flip;                     /* mirror left-right, after the resize */
+  int32_t rotate;                   /* 0: none */
+  int32_t affine[6];                /* a0 a1 a2 a3 a4 a5, 16.16, half-pixel folded in */
+} miclip_aug_desc;
+
+/* miclip_preprocess with the reference's train transform
+ * (data/clip_transforms.py:36-49): per image the geometry of `mode`, then the
+ * mirror (transpose(FLIP_LEFT_RIGHT) of the resized image), then
+ * RandomRotation's Image.rotate(angle, NEAREST, expand=False, fillcolor=0) as
+ * Pillow's 16.16 fixed-point gather over the R x R image:
+ *   xin = (a2 + y*a1 + x*a0) >> 16, yin = (a5 + y*a4 + x*a3) >> 16
+ * in wrapping 32-bit arithmetic, the source pixel where it lies inside the
+ * image and 0 elsewhere; then RGB, ToTensor and Normalize. The random draws and
+ * the matrix are the caller's (miclip/augment.py); the result is a deterministic
+ * function of them, bit-exact with Pillow, and an image's result does not
+ * depend on the rest of the batch. augs: HOST array [B], copied like descs.
+ * Coefficient tables and the rotation's input live in handle-owned buffers that
+ * are reused from call to call. Errors: EINVAL for a bad descriptor, a box that
+ * leaves the image, a CROP box that is not R x R, more than 64 taps in either
+ * pass, an unknown mode. */
+int miclip_preprocess_aug(miclip_model* m, const uint8_t* pixels, const miclip_image_desc* descs,
+                          const miclip_aug_desc* augs, int32_t B, void* out, int32_t out_kind,
+                          void* stream);
+
 /* ---- cached-feature consumers: outlier scoring, fp32 ----
  * Replace the torch ops of tools/outlier_cleaning.py's scorers on the
  * embeddings cache; all pointers are device memory, calls stream-ordered.
