@@ -1088,6 +1088,65 @@ int miclip_kmeans_lloyd(const float* x, const int32_t* order, const int32_t* off
   return 0;
 }
 
+static bool tsne_n_ok(int32_t N, std::string& why) {
+  if (N < 4 || N > 16384) why = "N must be in 4..16384, got " + std::to_string(N);
+  return why.empty();
+}
+
+int64_t miclip_tsne_scratch_bytes(int32_t N) {
+  return (N < 4 || N > 16384) ? 0 : (int64_t)N * 64;
+}
+
+int miclip_tsne_affinities(const float* x, int32_t N, int32_t D, int32_t metric, float perplexity,
+                           float* P, float* beta, float* dist, void* scratch, void* stream) {
+  const std::pair<const void*, const char*> ptrs[] = {
+      {x, "x"}, {P, "P"}, {beta, "beta"}, {scratch, "scratch"}};
+  for (const auto& a : ptrs)
+    if (!a.first) return fail(MICLIP_EINVAL, std::string("null argument: ") + a.second);
+  std::string why;
+  if (!tsne_n_ok(N, why)) return fail(MICLIP_EINVAL, why);
+  if (metric < 0 || metric > 2)
+    return fail(MICLIP_EINVAL, "metric must be 0 (cosine), 1 (euclidean) or 2 (precomputed), got " +
+                                   std::to_string(metric));
+  if (metric != 2 && (D < 1 || D > 4096))
+    return fail(MICLIP_EINVAL, "D must be in 1..4096, got " + std::to_string(D));
+  if (!(perplexity >= 1.f && perplexity < (float)N))
+    return fail(MICLIP_EINVAL, "perplexity must be in [1, N), got " + std::to_string(perplexity));
+  MICLIP_HIP(tsne_affinities(x, N, D, metric, perplexity, P, beta, dist, scratch,
+                             (hipStream_t)stream));
+  return 0;
+}
+
+int miclip_tsne_run(const float* P, int32_t N, float* y, float* update, float* gains,
+                    int32_t n_steps, float exaggeration, float momentum, float learning_rate,
+                    float min_gain, int32_t error_every, void* scratch, float* stats,
+                    void* stream) {
+  const std::pair<const void*, const char*> ptrs[] = {
+      {P, "P"}, {y, "y"}, {update, "update"}, {gains, "gains"}, {scratch, "scratch"},
+      {stats, "stats"}};
+  for (const auto& a : ptrs)
+    if (!a.first) return fail(MICLIP_EINVAL, std::string("null argument: ") + a.second);
+  std::string why;
+  if (!tsne_n_ok(N, why)) return fail(MICLIP_EINVAL, why);
+  if (n_steps < 1)
+    return fail(MICLIP_EINVAL, "n_steps must be >= 1, got " + std::to_string(n_steps));
+  if (error_every < 0)
+    return fail(MICLIP_EINVAL, "error_every must be >= 0, got " + std::to_string(error_every));
+  if (!(std::isfinite(exaggeration) && exaggeration > 0.f))
+    return fail(MICLIP_EINVAL,
+                "exaggeration must be finite and > 0, got " + std::to_string(exaggeration));
+  if (!(momentum >= 0.f && momentum < 1.f))
+    return fail(MICLIP_EINVAL, "momentum must be in [0, 1), got " + std::to_string(momentum));
+  if (!(std::isfinite(learning_rate) && learning_rate > 0.f))
+    return fail(MICLIP_EINVAL,
+                "learning_rate must be finite and > 0, got " + std::to_string(learning_rate));
+  if (!(std::isfinite(min_gain) && min_gain > 0.f))
+    return fail(MICLIP_EINVAL, "min_gain must be finite and > 0, got " + std::to_string(min_gain));
+  MICLIP_HIP(tsne_run(P, N, y, update, gains, n_steps, exaggeration, momentum, learning_rate,
+                      min_gain, error_every, scratch, stats, (hipStream_t)stream));
+  return 0;
+}
+
 int miclip_prolip_grad(const void* x, int32_t x_dtype, const int64_t* labels, int32_t n, int32_t D,
                        int32_t E, int32_t C, const float* text_weights, const float* P,
                        int32_t G, float scale, float* dZ, float* partials, void* stream) {

@@ -187,6 +187,20 @@ hipError_t kmeans_lloyd(const float* x, const int32_t* order, const int32_t* off
                         float* inertia, int32_t* n_iter, int32_t* strict, int32_t* counts,
                         hipStream_t s);
 
+// ---- exact t-SNE for the embedding-cache visualiser (tsne.hip), fp32 ----
+// 4 <= N <= 16384, 1 <= D <= 4096 (metric 0 cosine, 1 euclidean; 2: x is the [N, N]
+// matrix to use as it is and D is ignored), else hipErrorInvalidValue. scratch: 64 N bytes.
+// tsne_affinities: dist [N, N] (null: not kept), the perplexity search per row -> beta [N],
+// and the joint P [N, N], bit-symmetric with a zero diagonal.
+hipError_t tsne_affinities(const float* x, int N, int D, int metric, float perplexity, float* P,
+                           float* beta, float* dist, void* scratch, hipStream_t s);
+// tsne_run: n_steps iterations of scikit-learn's _gradient_descent on y [N, 2] (in/out, with
+// update and gains), two launches each, no host synchronisation. stats [4] = {KL, |grad|_2,
+// Z, steps done} is written after every error_every-th step (0: after the last one only).
+hipError_t tsne_run(const float* P, int N, float* y, float* update, float* gains, int n_steps,
+                    float exaggeration, float momentum, float lr, float min_gain, int error_every,
+                    void* scratch, float* stats, hipStream_t s);
+
 // ---- ProLIP projector training on cached features (prolip.hip), fp32 ----
 // One optimiser step of G configurations that share x [n, D] (x_dtype kIn32 / kF16 /
 // kBF16, 16-B aligned), labels [n] in [0, C), W [E, C] and P0 [D, E] and differ in

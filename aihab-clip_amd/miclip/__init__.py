@@ -13,10 +13,11 @@ import warnings
 
 import torch
 
-from . import augment, evaluation
+from . import augment, embed_vis, evaluation
 from .augment import build_clip_transforms
 from .configs import (MODEL_CONFIGS, OPEN_CLIP_MODELS, CLIPConfig, available_models,
                       config_from_state_dict)
+from .embed_vis import TsneResult, pca_reduce, tsne, visualize_cache
 from .evaluation import (ClassificationTracker, Evaluator, L2MetricsAccumulator,
                          aggregate_logits_to_l2, evaluate_features, map_l3_targets_to_l2,
                          run_validation)
@@ -28,7 +29,8 @@ __all__ = ["available_models", "load", "tokenize", "build_model", "CLIP", "CLIPC
            "MODEL_CONFIGS", "SeededWeightsWarning", "evaluation", "run_validation",
            "evaluate_features", "Evaluator", "L2MetricsAccumulator", "ClassificationTracker",
            "aggregate_logits_to_l2", "map_l3_targets_to_l2", "augment",
-           "build_clip_transforms"]
+           "build_clip_transforms", "embed_vis", "tsne", "pca_reduce", "visualize_cache",
+           "TsneResult"]
 
 
 class SeededWeightsWarning(UserWarning):

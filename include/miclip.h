@@ -296,6 +296,44 @@ int miclip_kmeans_lloyd(const float* x, const int32_t* order, const int32_t* off
                         float* scratch, float* centres, int32_t* labels, float* inertia,
                         int32_t* n_iter, int32_t* strict, int32_t* counts, void* stream);
 
+/* ---- exact t-SNE for the embedding-cache visualiser, fp32 ----
+ * Replace sklearn.manifold.TSNE(n_components=2, perplexity, metric, init).fit_transform
+ * of feat_cache_vis/feat_vis.py:150-157 by its exact form on the device: dense P,
+ * all-pairs repulsion, no tree and no neighbour truncation, one Student-t degree of
+ * freedom. The arithmetic rules are scikit-learn 1.7's (_t_sne.py, _utils.pyx).
+ * Limits: 4 <= N <= 16384, 1 <= D <= 4096, 1 <= perplexity < N, n_steps >= 1,
+ * error_every >= 0, learning_rate and min_gain finite and > 0, exaggeration finite
+ * and > 0, 0 <= momentum < 1, no NULL pointer except `dist`; anything else is
+ * MICLIP_EINVAL with the argument named in miclip_last_error, before any launch.
+ * All pointers are caller-owned device memory (scratch: miclip_tsne_scratch_bytes(N)
+ * bytes, 16-byte aligned, shared by both calls; 0 for an N outside the limits). The
+ * calls are stream-ordered, never synchronise and never allocate. There are no float
+ * atomics: results are bit-identical run to run.
+ *
+ * miclip_tsne_affinities (TSNE._fit's pairwise_distances + _joint_probabilities):
+ * metric 0 cosine -- clip(1 - cos, 0, 2) with a zero diagonal (cosine_distances), then
+ * squared as _t_sne.py:945-946 squares every non-euclidean metric; 1 euclidean --
+ * squared distance clamped at 0, zero diagonal; 2 precomputed -- x is the [N, N]
+ * matrix the search is fed as it is, D is ignored. dist (may be NULL) receives that
+ * matrix. Per row _binary_search_perplexity (beta from 1, at most 100 steps, tolerance
+ * 1e-5 on the entropy, sums in fp64) -> beta [N]; then P = max((C + C^T) / max(sum,
+ * eps), eps) off the diagonal, 0 on it, eps = 2^-52; P [N, N] is bit-symmetric. */
+int64_t miclip_tsne_scratch_bytes(int32_t N);
+int miclip_tsne_affinities(const float* x, int32_t N, int32_t D, int32_t metric, float perplexity,
+                           float* P, float* beta, float* dist, void* scratch, void* stream);
+/* miclip_tsne_run (_gradient_descent over _kl_divergence, _t_sne.py): n_steps
+ * iterations on y [N, 2] (in/out) with its `update` and `gains` [N, 2] (in/out).
+ * g = 4 (exaggeration * sum_j p w (y_i - y_j) - sum_j w^2 (y_i - y_j) / Z), w = 1 /
+ * (1 + |y_i - y_j|^2), Z = sum_{i != j} w; gains += 0.2 where update * g < 0, else
+ * *= 0.8, clipped at min_gain; update = momentum * update - learning_rate * gains * g;
+ * y += update. stats [4] = {KL error (of exaggeration * P), |gains * g|_2, Z, steps
+ * done by this call} is written after every error_every-th step, or after the last
+ * step only when error_every is 0. Two launches per step, no host synchronisation. */
+int miclip_tsne_run(const float* P, int32_t N, float* y, float* update, float* gains,
+                    int32_t n_steps, float exaggeration, float momentum, float learning_rate,
+                    float min_gain, int32_t error_every, void* scratch, float* stats,
+                    void* stream);
+
 /* ---- ProLIP projector training on the pre-projection feature cache, fp32 ----
  * One optimiser step of G configurations (the (lr, lambda) grid of search_lr,
  * or G = 1) per pair of calls. They share x [n, D] (x_dtype MICLIP_F32,
