@@ -9,8 +9,9 @@
 // The N x N score matrix is never materialised (online softmax, fp32).
 //
 // CDNA4 design:
-//   * one workgroup per (image, head); the head's whole K and V (N <= 608 keys,
-//     64 dims) are staged once into LDS and shared by all waves;
+//   * one workgroup per (image, head); the head's whole K and V (N <= 640 keys
+//     of 64 dims: 2 x 80 KiB, or N <= 416 of 80 dims in 192-B rows) are staged
+//     once into LDS and shared by all waves;
 //   * each wave owns 32-query chunks; S^T = K . Q^T with
 //     v_mfma_f32_32x32x16 (swapped operands, cdna_hip_programming.md T12): the
 //     query sits on the MFMA lane, so the softmax row max/sum over keys is an
@@ -1630,8 +1631,10 @@ hipError_t attn_launch(const void* qkv, void* out, int B, int N, int H, int dh, 
                        (T*)out, B, N, H, Npad, hpw, 0.125f, attn_prio());
     return hipGetLastError();
   }
-  // pipelined kernel (default; variant 2): two K/V buffers must fit in LDS
-  // (N <= 320). ViT-L/14 layer: 0.19-0.21 ms vs 0.21-0.24 ms one head per WG.
+  // pipelined kernel (default; variant 2): two K/V buffers and the split form's
+  // partials must fit in LDS (Npad <= 288: at 320 the buffers alone fill the 160
+  // KiB). Above that variants 0, 2 and 4 run the one-head kernel below.
+  // ViT-L/14 layer: 0.19-0.21 ms vs 0.21-0.24 ms one head per WG.
   if (variant != 1 && variant != 3 && variant < 10 && 2 * lds + 2 * 10 * 2 * 66 * 4 <= 160 * 1024) {
     static bool attr_set = false;
     if (!attr_set) {

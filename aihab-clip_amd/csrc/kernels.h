@@ -92,12 +92,17 @@ hipError_t ln_fold(int dtype, const void* W, const float* gamma, const float* be
 // qkv: [B*N, 3*H*dh] compute dtype (torch in_proj order q|k|v); out: [B*N, H*dh].
 // head dim dh = 64 (OpenAI CLIP) or 80 (open_clip ViT-H/14 vision tower; one head
 // per workgroup); causal adds the -inf strictly-upper-triangular mask
-// (clip/model.py:323-329). variant (dh 64): 0 = default (the two-workgroup x8
-// kernel for N in 256..259, else the pipelined multi-head kernel when N <= 320,
-// one head per workgroup above), 1 = one head per workgroup, 2 = pipelined,
-// 4 = pipelined + last-chunk split, 8 = x8, 10-16 = one head per workgroup on
-// that many waves (probe). variant (dh 80): 0 = default (the two-phase kernel where
-// it applies), 1 = attention_kernel<80>, 2 = two-phase.
+// (clip/model.py:323-329). N <= 640 (dh 64) or 416 (dh 80): a head's K and V sit
+// in LDS whole; above that every variant is refused. variant (dh 64): 0 = default
+// (the two-workgroup x8 kernel for non-causal N in 256..259, else the pipelined
+// multi-head kernel while two K/V buffers fit, i.e. N padded to 32 <= 288, one head
+// per workgroup above), 1 = one head per workgroup, 2 = pipelined, 4 = pipelined +
+// last-chunk split (2 and 4 above N = 288: the one-head kernel, not a refusal),
+// 8 = x8 (refused outside non-causal 256..259), 10-16 = one head per workgroup on
+// that many waves (probe). variant (dh 80): 0 = default (the pipelined kernel at
+// non-causal N in 256..259, else the two-phase kernel where it applies: non-causal
+// N in 129..288), 1 = attention_kernel<80>, 2 = two-phase, 6 = pipelined (2 and 6
+// are refused where they do not apply).
 hipError_t attention(int dtype, const void* qkv, void* out, int B, int N, int H, int causal,
                      hipStream_t s, int variant = 0, int head_dim = 64);
 
