@@ -553,8 +553,10 @@ int ensure_aux(miclip_model* m, int n) {
 }
 
 // encode_image for B images whose workspace window is `w` (clip/model.py:216-235)
+// trunk_out (fine-tuning): stop in front of the last vision block and copy the
+// residual stream [B * N, W] there instead
 int encode_image_part(miclip_model* m, Workspace w, const void* images, int in_dt, int B,
-                      void* out, uint32_t flags, hipStream_t s) {
+                      void* out, uint32_t flags, hipStream_t s, void* trunk_out = nullptr) {
   const auto& c = m->cfg;
   const int P = c.vision_patch_size, R = c.image_resolution, W = c.vision_width;
   const int dh = c.vision_head_dim, g = R / P, np = g * g, N = np + 1, H = W / dh;
@@ -585,10 +587,15 @@ int encode_image_part(miclip_model* m, Workspace w, const void* images, int in_d
   // the last block on the CLS rows only (run_block); N beyond attention_q0's
   // range (never for CLIP's towers) runs it whole
   const bool cls_last = m->cls_last && N <= 768;
-  for (int l = 0; l < c.vision_layers; ++l)
+  for (int l = 0; l < c.vision_layers - (trunk_out ? 1 : 0); ++l)
     if ((rc = run_block(m, m->vblocks[l], w, B, N, W, H, dh, 0, s,
                         cls_last && l == c.vision_layers - 1)))
       return rc;
+  if (trunk_out) {
+    MICLIP_HIP(hipMemcpyAsync(trunk_out, w.x, (size_t)M * W * (m->resid16 ? 2 : 4),
+                              hipMemcpyDeviceToDevice, s));
+    return 0;
+  }
   const bool proj = flags & MICLIP_FLAG_APPLY_PROJ, norm = flags & MICLIP_FLAG_NORMALIZE;
   // ln_post on the CLS rows only (clip/model.py:228): rows b*N of x, or the
   // compact CLS block xc
@@ -906,6 +913,28 @@ int miclip_encode_image_ex(miclip_model* m, const void* images, int32_t image_dt
   return 0;
 }
 
+int miclip_encode_image_trunk(miclip_model* m, const void* images, int32_t image_dtype, int32_t B,
+                              void* x_out, void* stream) {
+  if (!m) return fail(MICLIP_EINVAL, "null argument: model");
+  if (!images) return fail(MICLIP_EINVAL, "null argument: images");
+  if (!x_out) return fail(MICLIP_EINVAL, "null argument: x_out");
+  if (B < 1) return fail(MICLIP_EINVAL, "B: expected B >= 1");
+  if (image_dtype != MICLIP_F32 && image_dtype != MICLIP_FP16 && image_dtype != MICLIP_BF16)
+    return fail(MICLIP_EINVAL, "image_dtype must be MICLIP_F32, MICLIP_FP16 or MICLIP_BF16");
+  if (m->mx) return fail(MICLIP_EINVAL, "model: an MX-fp8 model has no trunk output (fp16 / bf16 only)");
+  if (m->cfg.vision_layers < 1) return fail(MICLIP_EINVAL, "model: no vision block");
+  const int in_dt = image_dtype == MICLIP_F32 ? kIn32 : image_dtype == MICLIP_FP16 ? kF16 : kBF16;
+  if (!tower_loaded(m, true))
+    return fail(MICLIP_ENOWEIGHTS, "visual weights not loaded (missing " + missing(m, true) + ")");
+  if (int rc0 = ensure_folded(m, true)) return rc0;
+  const auto& c = m->cfg;
+  const int g = c.image_resolution / c.vision_patch_size, N = g * g + 1, W = c.vision_width;
+  if (int rc = ensure_ws(m, m->wimg, B, N, W, true)) return rc;
+  // one stream: a row of x depends on its image alone, whatever the batch
+  return encode_image_part(m, view(m, m->wimg, 0, 0, N, W), images, in_dt, B, nullptr, 0,
+                           (hipStream_t)stream, x_out);
+}
+
 int miclip_image_splits(const miclip_model* m, int32_t B) {
   if (!m || B < 1) return fail(MICLIP_EINVAL, "bad argument to image_splits");
   const int g = m->cfg.image_resolution / m->cfg.vision_patch_size;
@@ -1168,6 +1197,146 @@ int miclip_prolip_adam(const void* x, int32_t x_dtype, const float* dZ, int32_t 
   MICLIP_HIP(prolip_adam(x_dtype, x, dZ, P0, P, m, v, lr, lambda, grad_partials, mse_partials,
                          history, n, D, E, G, lr_factor, lambda_div, step, eps,
                          (hipStream_t)stream));
+  return 0;
+}
+
+// ---- last-block fine-tuning (finetune.hip) ----
+static bool gemm_tn_args_ok(int32_t M, int32_t Nn, int32_t K, std::string& why) {
+  if (M < 1 || M > 0x7fffffff - 64) why = "M: expected M >= 1";
+  else if (Nn < 16 || Nn > 65536 || Nn % 16) why = "Nn: expected a multiple of 16 in [16, 65536]";
+  else if (K < 16 || K > 65536 || K % 16) why = "K: expected a multiple of 16 in [16, 65536]";
+  return why.empty();
+}
+
+int64_t miclip_gemm_tn_ws_bytes(int32_t M, int32_t Nn, int32_t K) {
+  return (int64_t)gemm_tn_ws_bytes(M, Nn, K);
+}
+
+int miclip_gemm_tn_plan(int32_t M, int32_t Nn, int32_t K, int32_t* slices, int32_t* slice_rows) {
+  std::string why;
+  if (!gemm_tn_args_ok(M, Nn, K, why)) return fail(MICLIP_EINVAL, why);
+  if (!slices) return fail(MICLIP_EINVAL, "null argument: slices");
+  if (!slice_rows) return fail(MICLIP_EINVAL, "null argument: slice_rows");
+  int S, rows;
+  gemm_tn_plan(M, Nn, K, &S, &rows);
+  *slices = S;
+  *slice_rows = rows;
+  return 0;
+}
+
+int miclip_op_gemm_tn(int32_t dtype, const void* A, const void* X, float* G, int32_t M, int32_t Nn,
+                      int32_t K, void* workspace, void* stream) {
+  std::string why;
+  if (dtype != MICLIP_FP16 && dtype != MICLIP_BF16)
+    return fail(MICLIP_EINVAL, "dtype: expected MICLIP_FP16 or MICLIP_BF16");
+  if (!gemm_tn_args_ok(M, Nn, K, why)) return fail(MICLIP_EINVAL, why);
+  if (!A) return fail(MICLIP_EINVAL, "null argument: A");
+  if (!X) return fail(MICLIP_EINVAL, "null argument: X");
+  if (!G) return fail(MICLIP_EINVAL, "null argument: G");
+  if (!workspace) return fail(MICLIP_EINVAL, "null argument: workspace");
+  if (((uintptr_t)A & 15) || ((uintptr_t)X & 15))
+    return fail(MICLIP_EINVAL, "A / X: expected 16-byte aligned operands");
+  MICLIP_HIP(gemm_tn(dtype, A, X, G, M, Nn, K, (float*)workspace, nullptr, (hipStream_t)stream));
+  return 0;
+}
+
+int miclip_ft_adam(float* params, const float* grads, float* m, float* v, int64_t numel, float lr,
+                   int32_t step, float eps, void* stream) {
+  if (numel < 1 || numel > ((int64_t)1 << 38)) return fail(MICLIP_EINVAL, "numel: expected numel >= 1");
+  if (step < 1) return fail(MICLIP_EINVAL, "step: expected the 1-based step count");
+  if (!(lr >= 0.f)) return fail(MICLIP_EINVAL, "lr: expected lr >= 0");
+  if (!(eps >= 0.f)) return fail(MICLIP_EINVAL, "eps: expected eps >= 0");
+  if (!params) return fail(MICLIP_EINVAL, "null argument: params");
+  if (!grads) return fail(MICLIP_EINVAL, "null argument: grads");
+  if (!m) return fail(MICLIP_EINVAL, "null argument: m");
+  if (!v) return fail(MICLIP_EINVAL, "null argument: v");
+  MICLIP_HIP(ft_adam(params, grads, m, v, numel, lr, step, eps, (hipStream_t)stream));
+  return 0;
+}
+
+static bool ft_proj_args_ok(int32_t B, int32_t W, int32_t E, int32_t C, std::string& why) {
+  if (B < 1 || B > (1 << 24)) why = "B: expected 1 <= B <= 2^24";
+  else if (W < 128 || W > 1280 || W % 128) why = "W: expected a multiple of 128 in [128, 1280]";
+  else if (E < 16 || E > 1024 || E % 16) why = "E: expected a multiple of 16 in [16, 1024]";
+  else if (C < 1 || C > 1024) why = "C: expected 1 <= C <= 1024";
+  return why.empty();
+}
+
+int64_t miclip_ft_proj_scratch_bytes(int32_t B, int32_t W, int32_t E, int32_t C) {
+  return (int64_t)ft_proj_scratch_bytes(B, W, E, C);
+}
+
+int miclip_ft_proj_grad(const float* y, const int64_t* labels, const float* text_weights,
+                        const float* proj, int32_t B, int32_t W, int32_t E, int32_t C,
+                        int32_t compute_dtype, float scale, float* dP, void* scratch, float* stats,
+                        void* stream) {
+  std::string why;
+  if (!ft_proj_args_ok(B, W, E, C, why)) return fail(MICLIP_EINVAL, why);
+  if (compute_dtype != MICLIP_FP16 && compute_dtype != MICLIP_BF16)
+    return fail(MICLIP_EINVAL, "compute_dtype: expected MICLIP_FP16 or MICLIP_BF16");
+  if (!y) return fail(MICLIP_EINVAL, "null argument: y");
+  if (!labels) return fail(MICLIP_EINVAL, "null argument: labels");
+  if (!text_weights) return fail(MICLIP_EINVAL, "null argument: text_weights");
+  if (!proj) return fail(MICLIP_EINVAL, "null argument: proj");
+  if (!dP) return fail(MICLIP_EINVAL, "null argument: dP");
+  if (!scratch) return fail(MICLIP_EINVAL, "null argument: scratch");
+  if (!stats) return fail(MICLIP_EINVAL, "null argument: stats");
+  if (((uintptr_t)scratch & 255) || ((uintptr_t)y & 15))
+    return fail(MICLIP_EINVAL, "scratch / y: expected 256-byte / 16-byte alignment");
+  MICLIP_HIP(ft_proj_grad(compute_dtype, y, labels, text_weights, proj, B, W, E, C, scale, dP,
+                          scratch, stats, (hipStream_t)stream));
+  return 0;
+}
+
+static bool ft_args_ok(int32_t B, int32_t N, int32_t W, int32_t E, int32_t C, int32_t dh,
+                       std::string& why) {
+  if (!ft_proj_args_ok(B, W, E, C, why)) return false;
+  if (N < 1 || N > 768) why = "N: expected 1 <= N <= 768";
+  else if (dh != 64 && dh != 80) why = "head_dim: expected 64 or 80";
+  else if (W % dh) why = "W: expected a multiple of head_dim";
+  else if ((int64_t)B * N > 0x7fffffff - 64) why = "B: B * N exceeds 2^31";
+  return why.empty();
+}
+
+int miclip_ft_layout(int32_t W, int32_t E, int64_t* offsets) {
+  if (W < 128 || W > 1280 || W % 128) return fail(MICLIP_EINVAL, "W: expected a multiple of 128 in [128, 1280]");
+  if (E < 16 || E > 1024 || E % 16) return fail(MICLIP_EINVAL, "E: expected a multiple of 16 in [16, 1024]");
+  if (!offsets) return fail(MICLIP_EINVAL, "null argument: offsets");
+  ft_layout(W, E, offsets);
+  return 0;
+}
+
+int64_t miclip_ft_scratch_bytes(int32_t B, int32_t N, int32_t W, int32_t E, int32_t C,
+                                int32_t head_dim) {
+  return (int64_t)ft_scratch_bytes(B, N, W, E, C, head_dim);
+}
+
+int miclip_ft_grad(const void* x, int32_t x_dtype, const int64_t* labels,
+                   const float* text_weights, const float* params, int32_t B, int32_t N,
+                   int32_t W, int32_t E, int32_t C, int32_t head_dim, int32_t act,
+                   int32_t compute_dtype, float scale, int32_t groups, float* grads,
+                   void* scratch, float* stats, float* feats, void* stream) {
+  std::string why;
+  if (!ft_args_ok(B, N, W, E, C, head_dim, why)) return fail(MICLIP_EINVAL, why);
+  if (groups != 1 && groups != 2) return fail(MICLIP_EINVAL, "groups: expected 1 or 2");
+  if (compute_dtype != MICLIP_FP16 && compute_dtype != MICLIP_BF16)
+    return fail(MICLIP_EINVAL, "compute_dtype: expected MICLIP_FP16 or MICLIP_BF16");
+  if (x_dtype != MICLIP_FP16 && x_dtype != MICLIP_F32)
+    return fail(MICLIP_EINVAL, "x_dtype: expected MICLIP_FP16 or MICLIP_F32 (the stream types)");
+  if (act != MICLIP_ACT_QUICKGELU && act != MICLIP_ACT_GELU)
+    return fail(MICLIP_EINVAL, "act: expected MICLIP_ACT_QUICKGELU or MICLIP_ACT_GELU");
+  if (!x) return fail(MICLIP_EINVAL, "null argument: x");
+  if (!labels) return fail(MICLIP_EINVAL, "null argument: labels");
+  if (!text_weights) return fail(MICLIP_EINVAL, "null argument: text_weights");
+  if (!params) return fail(MICLIP_EINVAL, "null argument: params");
+  if (!grads) return fail(MICLIP_EINVAL, "null argument: grads");
+  if (!scratch) return fail(MICLIP_EINVAL, "null argument: scratch");
+  if (!stats) return fail(MICLIP_EINVAL, "null argument: stats");
+  if ((uintptr_t)scratch & 255) return fail(MICLIP_EINVAL, "scratch: expected 256-byte alignment");
+  MICLIP_HIP(ft_grad(compute_dtype, x_dtype == MICLIP_FP16 ? kF16 : kIn32, x, labels,
+                     text_weights, params, B, N, W, E, C, head_dim,
+                     act == MICLIP_ACT_GELU ? ACT_GELU : ACT_QUICKGELU, scale, groups, grads,
+                     scratch, stats, feats, (hipStream_t)stream));
   return 0;
 }
 

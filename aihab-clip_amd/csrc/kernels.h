@@ -228,6 +228,46 @@ hipError_t prolip_adam(int x_dtype, const void* x, const float* dZ, const float*
                        int E, int G, float lr_factor, float lambda_div, int step, float eps,
                        hipStream_t s);
 
+// ---- last-block fine-tuning of the image tower (finetune.hip) ----
+// gemm_tn: G [Nn, K] fp32 = sum_m A[m, Nn] * X[m, K] (A, X compute dtype, row-major,
+// 16-B aligned; both contracted along rows), times *out_scale (device, nullable).
+// Nn, K % 16 == 0, 16 <= Nn, K <= 65536, M >= 1. M is split into `slices` slices of
+// `slice_rows` rows (gemm_tn_plan, a function of the shape only) through the fp32
+// workspace ws of gemm_tn_ws_bytes, summed in ascending slice order.
+bool gemm_tn_shape_ok(int64_t M, int64_t Nn, int64_t K);
+void gemm_tn_plan(int M, int Nn, int K, int* slices, int* slice_rows);
+size_t gemm_tn_ws_bytes(int M, int Nn, int K);   // 0 for an unsupported shape
+hipError_t gemm_tn(int dtype, const void* A, const void* X, float* G, int M, int Nn, int K,
+                   float* ws, const float* out_scale, hipStream_t s);
+// torch.optim.Adam's step `step` (1-based; betas 0.9 / 0.999, no weight decay) with the
+// rate lr over one contiguous fp32 block of numel elements.
+hipError_t ft_adam(float* params, const float* grads, float* m, float* v, int64_t numel, float lr,
+                   int step, float eps, hipStream_t s);
+// Group 1 (visual.proj) of the tail: y [B, W] fp32 = ln_post of the CLS rows, proj [W, E]
+// the fp32 master; loss = mean CE of scale * normalize(y proj) tw against labels.
+// dP [W, E] = d loss / d proj (operands y and dZ rounded once to the compute dtype, dZ
+// under a power-of-two scale), stats = {sum of row CE, correct count}.
+// W % 128 == 0, 128 <= W <= 1280, E % 16 == 0, 16 <= E <= 1024, 1 <= C <= 1024, B >= 1.
+bool ft_proj_shape_ok(int64_t B, int64_t W, int64_t E, int64_t C);
+size_t ft_proj_scratch_bytes(int B, int W, int E, int C);   // 0 for an unsupported shape
+hipError_t ft_proj_grad(int dtype, const float* y, const int64_t* labels, const float* tw,
+                        const float* proj, int B, int W, int E, int C, float scale, float* dP,
+                        void* scratch, float* stats, hipStream_t s);
+// Groups 1 and 2 from the residual stream x [B * N, W] (x_dtype kF16 or kIn32) entering the
+// last vision block: forward of the tail, loss, and the gradients of the unlocked groups
+// into grads (flat fp32 block laid out by ft_layout: the block's 12 tensors, ln_post's 2,
+// proj; offsets [kFtTensors + 1], the last one the total). groups 1 writes dP only. stats =
+// {sum of row CE, correct count}; y_out (nullable) [B, W] = ln_post of the CLS rows.
+// ft_proj_grad's limits, 1 <= N <= 768, dh 64 or 80 dividing W, act ACT_QUICKGELU / ACT_GELU.
+constexpr int kFtTensors = 15;
+void ft_layout(int W, int E, int64_t* offsets);
+bool ft_shape_ok(int64_t B, int64_t N, int64_t W, int64_t E, int64_t C, int64_t dh);
+size_t ft_scratch_bytes(int B, int N, int W, int E, int C, int dh);   // 0 outside the limits
+hipError_t ft_grad(int dtype, int x_dtype, const void* x, const int64_t* labels, const float* tw,
+                   const float* params, int B, int N, int W, int E, int C, int dh, int act,
+                   float scale, int groups, float* grads, void* scratch, float* stats,
+                   float* y_out, hipStream_t s);
+
 // ---- validation metrics (evaluate.hip), fp32 ----
 // The caller-owned state block, as 8-byte words (include/miclip.h documents it):
 // word 0 the float64 sum of batch-mean losses, words 1..7 integer counters, then the

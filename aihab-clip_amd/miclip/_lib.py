@@ -48,6 +48,9 @@ EXPORTS = (
     "miclip_kmeans_scratch_bytes", "miclip_kmeans_seed", "miclip_kmeans_lloyd",
     "miclip_tsne_scratch_bytes", "miclip_tsne_affinities", "miclip_tsne_run",
     "miclip_prolip_grad", "miclip_prolip_adam",
+    "miclip_gemm_tn_ws_bytes", "miclip_gemm_tn_plan", "miclip_op_gemm_tn", "miclip_ft_adam",
+    "miclip_ft_proj_scratch_bytes", "miclip_ft_proj_grad",
+    "miclip_encode_image_trunk", "miclip_ft_layout", "miclip_ft_scratch_bytes", "miclip_ft_grad",
     "miclip_eval_state_bytes", "miclip_eval_reset", "miclip_eval_batch",
     "miclip_mx_scale_bytes", "miclip_op_quant_mx", "miclip_op_gemm_mx", "miclip_op_gemm_mx_v", "miclip_op_layernorm_mx",
 )
@@ -173,6 +176,19 @@ def load_library(path: str = None):
                                ctypes.c_int),
         "miclip_prolip_adam": ([vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, f32, f32,
                                 i32, f32, vp, vp, vp, vp], ctypes.c_int),
+        "miclip_gemm_tn_ws_bytes": ([i32, i32, i32], i64),
+        "miclip_gemm_tn_plan": ([i32, i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)],
+                                ctypes.c_int),
+        "miclip_op_gemm_tn": ([i32, vp, vp, vp, i32, i32, i32, vp, vp], ctypes.c_int),
+        "miclip_ft_adam": ([vp, vp, vp, vp, i64, f32, i32, f32, vp], ctypes.c_int),
+        "miclip_ft_proj_scratch_bytes": ([i32, i32, i32, i32], i64),
+        "miclip_ft_proj_grad": ([vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp],
+                                ctypes.c_int),
+        "miclip_encode_image_trunk": ([vp, vp, i32, i32, vp, vp], ctypes.c_int),
+        "miclip_ft_layout": ([i32, i32, ctypes.POINTER(i64)], ctypes.c_int),
+        "miclip_ft_scratch_bytes": ([i32, i32, i32, i32, i32, i32], i64),
+        "miclip_ft_grad": ([vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, f32, i32,
+                            vp, vp, vp, vp, vp], ctypes.c_int),
         "miclip_eval_state_bytes": ([i32, i32], i64),
         "miclip_eval_reset": ([vp, i32, i32, vp], ctypes.c_int),
         "miclip_eval_batch": ([vp, i32, vp, vp, i32, i32, i32, f32, vp, i32, i32, u32, vp, vp, vp,

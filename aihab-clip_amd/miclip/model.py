@@ -301,10 +301,13 @@ class CLIP(nn.Module):
                 for i in range(n) if arr[i].launches}
 
     # open_clip's training hooks (methods/PEFT_openclip.py:197-273 locks towers and
-    # backpropagates through encode_image): outside the inference path built here
+    # backpropagates through encode_image): outside the inference path built here.
+    # miclip.finetune trains the last two groups of the image tower without them.
     def lock_image_tower(self, *args, **kwargs):
         raise NotImplementedError("miclip is an inference path: open_clip's lock_image_tower / "
-                                  "PEFT training (backward through encode_image) is not supported")
+                                  "PEFT training (backward through encode_image) is not supported; "
+                                  "miclip.finetune.FTOpenCLIP / LastBlockTrainer train the image "
+                                  "tower's last two groups")
 
     def lock_text_tower(self, *args, **kwargs):
         raise NotImplementedError("miclip is an inference path: open_clip's lock_text_tower / "

@@ -24,10 +24,12 @@ open_clip's own code.
   * get_tokenizer(name) -> callable(texts, context_length=77): the CLIP BPE
     (open_clip's SimpleTokenizer is the same vocabulary and padding).
 
-Scope: the inference contract only -- model_init, feature caching and eval.
-The PEFT training loop (methods/PEFT_openclip.py:197-273: lock_image_tower /
-lock_text_tower, backward through encode_image) is outside the encode path; the
-model's lock_* methods raise NotImplementedError saying so.
+Scope: the inference contract -- model_init, feature caching and eval. The PEFT
+training loop (methods/PEFT_openclip.py:197-273) is `miclip.finetune.FTOpenCLIP`,
+for the image tower's last two groups (`unlocked_groups` 1 and 2, text tower
+frozen); it trains its own fp32 master copy and never calls the model's
+lock_image_tower / lock_text_tower, which keep raising NotImplementedError
+(a gradient through the whole of encode_image is not built).
 """
 import os
 import warnings

@@ -372,6 +372,94 @@ int miclip_prolip_adam(const void* x, int32_t x_dtype, const float* dZ, int32_t 
                        int32_t step, float eps, const float* grad_partials, float* mse_partials,
                        float* history, void* stream);
 
+/* ---- fine-tuning of the image tower's tail ----
+ * FTOpenCLIP's training step (methods/PEFT_openclip.py:247-274) for
+ * unlocked_groups 1 and 2 of lock_image_tower (:196-197): first the op-level
+ * pieces, then the trunk / tail entry points. Except miclip_encode_image_trunk
+ * they need no model handle; all are stream-ordered, never synchronise, never
+ * allocate after the scratch query and use no atomics: every result is
+ * bit-identical run to run. All pointers
+ * are device memory owned by the caller. Every limit below is checked before
+ * any launch: MICLIP_EINVAL with the argument named in miclip_last_error.
+ *
+ * miclip_op_gemm_tn: G [Nn, K] (fp32) = sum_m A[m, Nn] * X[m, K], A [M, Nn] and
+ * X [M, K] row-major in `dtype` (MICLIP_FP16 / MICLIP_BF16), 16-byte aligned,
+ * fp32 accumulation: the weight gradient dW = dY^T X that loss.backward()
+ * (:273) forms for every Linear. Nn % 16 == 0, K % 16 == 0, 16 <= Nn, K <=
+ * 65536, M >= 1 (the row tail is masked). M is split into `slices` slices of
+ * `slice_rows` rows (miclip_gemm_tn_plan; a function of (M, Nn, K) only) that
+ * are summed in ascending order through `workspace`, miclip_gemm_tn_ws_bytes
+ * bytes (0 for an unsupported shape). */
+int64_t miclip_gemm_tn_ws_bytes(int32_t M, int32_t Nn, int32_t K);
+int miclip_gemm_tn_plan(int32_t M, int32_t Nn, int32_t K, int32_t* slices, int32_t* slice_rows);
+int miclip_op_gemm_tn(int32_t dtype, const void* A, const void* X, float* G, int32_t M, int32_t Nn,
+                      int32_t K, void* workspace, void* stream);
+/* miclip_ft_adam replaces optimizer.step() (:274) of torch.optim.Adam(lr=lr_v)
+ * (:233) over one contiguous fp32 block params / grads / m / v of numel
+ * elements: betas 0.9 / 0.999, eps, bias correction by the 1-based `step`, no
+ * weight decay. lr is the scheduled rate, lr_v * 0.5 (1 + cos(pi epoch / T))
+ * under CosineAnnealingLR (:234). numel >= 1, step >= 1, lr >= 0, eps >= 0. */
+int miclip_ft_adam(float* params, const float* grads, float* m, float* v, int64_t numel, float lr,
+                   int32_t step, float eps, void* stream);
+/* miclip_ft_proj_grad replaces :250-251, :262-266 and the backward (:273) for
+ * visual.proj: with y [B, W] fp32 the pre-projection features (ln_post of the
+ * CLS rows, miclip_encode_image without MICLIP_FLAG_APPLY_PROJ) and proj [W, E]
+ * the fp32 master, logits = scale * normalize(y @ proj) @ text_weights ([E, C]),
+ * loss = cross_entropy(logits, labels) (mean), dP [W, E] = d loss / d proj.
+ * The forward runs in fp32 (as miclip_prolip_grad); the operands of dP = y^T dZ
+ * are rounded once (RNE) to compute_dtype, dZ under a power-of-two scale that
+ * is undone in fp32. stats [2] receives {sum of the rows' cross-entropy, number
+ * of rows with argmax(logits) == label}. labels [B] int64 in [0, C).
+ * W % 128 == 0, 128 <= W <= 1280, E % 16 == 0, 16 <= E <= 1024, 1 <= C <=
+ * 1024, 1 <= B <= 2^24, compute_dtype MICLIP_FP16 / MICLIP_BF16; scratch is
+ * miclip_ft_proj_scratch_bytes bytes (0 outside the limits), 256-byte aligned. */
+int64_t miclip_ft_proj_scratch_bytes(int32_t B, int32_t W, int32_t E, int32_t C);
+int miclip_ft_proj_grad(const float* y, const int64_t* labels, const float* text_weights,
+                        const float* proj, int32_t B, int32_t W, int32_t E, int32_t C,
+                        int32_t compute_dtype, float scale, float* dP, void* scratch, float* stats,
+                        void* stream);
+/* Groups 1 and 2: visual.proj, and visual.transformer.resblocks.{L-1}.* with
+ * visual.ln_post.* (counted from the back as open_clip's VisionTransformer.lock;
+ * parity with open_clip unpinned).
+ *
+ * miclip_encode_image_trunk runs encode_image (clip/model.py:216-226) up to, but
+ * not including, the last vision block and copies the residual stream [B * N, W]
+ * to x_out in the handle's stream type (fp16, or fp32 under MICLIP_OPT_RESID_F32;
+ * miclip_model_flags): the frozen part of :250 when lock_image_tower(
+ * unlocked_groups <= 2) (:197) holds. One stream; a row depends on its image alone.
+ *
+ * miclip_ft_layout: element offsets of the 15 trainable tensors in the flat fp32
+ * block, in named_parameters order -- the last block's ln_1.weight, ln_1.bias,
+ * attn.in_proj_weight, attn.in_proj_bias, attn.out_proj.weight, attn.out_proj.bias,
+ * ln_2.weight, ln_2.bias, mlp.c_fc.weight, mlp.c_fc.bias, mlp.c_proj.weight,
+ * mlp.c_proj.bias, then ln_post.weight, ln_post.bias, then proj [W, E] -- and the
+ * total in offsets[15].
+ *
+ * miclip_ft_grad replaces the rest of :250-266 and loss.backward() (:273): the
+ * last block on the CLS rows (clip/model.py:183-186, 226-229), ln_post, proj,
+ * normalise, scale * f @ text_weights, mean cross-entropy, and the gradients of
+ * the unlocked groups into `grads` (same layout; groups = 1 writes proj's slice
+ * only). x [B * N, W] is the trunk's output (x_dtype MICLIP_FP16 or MICLIP_F32)
+ * and carries no gradient, so the token-row side of the backward is one TN GEMM
+ * dQKV^T . xhat. Master parameters and gradients fp32; GEMM operands rounded
+ * once (RNE) to compute_dtype, gradient operands under a power-of-two scale;
+ * LayerNorm statistics, softmax, activation derivatives, normalise and loss fp32.
+ * stats [2] = {sum of the rows' cross-entropy, correct count}; feats (nullable)
+ * [B, W] receives ln_post of the CLS rows (the pre-projection features).
+ * Limits: those of miclip_ft_proj_grad, 1 <= N <= 768, head_dim 64 or 80 dividing
+ * W, act MICLIP_ACT_QUICKGELU / MICLIP_ACT_GELU, groups 1 or 2; scratch is
+ * miclip_ft_scratch_bytes bytes (0 outside the limits), 256-byte aligned. */
+int miclip_encode_image_trunk(miclip_model* model, const void* images, int32_t image_dtype,
+                              int32_t B, void* x_out, void* stream);
+int miclip_ft_layout(int32_t W, int32_t E, int64_t* offsets);
+int64_t miclip_ft_scratch_bytes(int32_t B, int32_t N, int32_t W, int32_t E, int32_t C,
+                                int32_t head_dim);
+int miclip_ft_grad(const void* x, int32_t x_dtype, const int64_t* labels,
+                   const float* text_weights, const float* params, int32_t B, int32_t N,
+                   int32_t W, int32_t E, int32_t C, int32_t head_dim, int32_t act,
+                   int32_t compute_dtype, float scale, int32_t groups, float* grads,
+                   void* scratch, float* stats, float* feats, void* stream);
+
 /* ---- validation metrics on features or logits, fp32 ----
  * Replace the body of _run_validation's batch loop (methods/PEFT_openclip.py:
  * 89-117) and the per-batch work of aihab_utils/evaluation.py (cls_acc top-1 /
