@@ -1311,32 +1311,75 @@ int64_t miclip_ft_scratch_bytes(int32_t B, int32_t N, int32_t W, int32_t E, int3
   return (int64_t)ft_scratch_bytes(B, N, W, E, C, head_dim);
 }
 
+// the checks miclip_ft_grad and miclip_ft_grad_rows share; x_name names the stream argument
+static bool ft_grad_args_ok(const char* x_name, const void* x, int32_t x_dtype,
+                            const int64_t* labels, const float* text_weights, const float* params,
+                            int32_t B, int32_t N, int32_t W, int32_t E, int32_t C, int32_t head_dim,
+                            int32_t act, int32_t compute_dtype, int32_t groups, const float* grads,
+                            const void* scratch, const float* stats, std::string& why) {
+  if (!ft_args_ok(B, N, W, E, C, head_dim, why)) return false;
+  if (groups != 1 && groups != 2) why = "groups: expected 1 or 2";
+  else if (compute_dtype != MICLIP_FP16 && compute_dtype != MICLIP_BF16)
+    why = "compute_dtype: expected MICLIP_FP16 or MICLIP_BF16";
+  else if (x_dtype != MICLIP_FP16 && x_dtype != MICLIP_F32)
+    why = "x_dtype: expected MICLIP_FP16 or MICLIP_F32 (the stream types)";
+  else if (act != MICLIP_ACT_QUICKGELU && act != MICLIP_ACT_GELU)
+    why = "act: expected MICLIP_ACT_QUICKGELU or MICLIP_ACT_GELU";
+  else if (!x) why = std::string("null argument: ") + x_name;
+  else if (!labels) why = "null argument: labels";
+  else if (!text_weights) why = "null argument: text_weights";
+  else if (!params) why = "null argument: params";
+  else if (!grads) why = "null argument: grads";
+  else if (!scratch) why = "null argument: scratch";
+  else if (!stats) why = "null argument: stats";
+  else if ((uintptr_t)scratch & 255) why = "scratch: expected 256-byte alignment";
+  return why.empty();
+}
+
 int miclip_ft_grad(const void* x, int32_t x_dtype, const int64_t* labels,
                    const float* text_weights, const float* params, int32_t B, int32_t N,
                    int32_t W, int32_t E, int32_t C, int32_t head_dim, int32_t act,
                    int32_t compute_dtype, float scale, int32_t groups, float* grads,
                    void* scratch, float* stats, float* feats, void* stream) {
   std::string why;
-  if (!ft_args_ok(B, N, W, E, C, head_dim, why)) return fail(MICLIP_EINVAL, why);
-  if (groups != 1 && groups != 2) return fail(MICLIP_EINVAL, "groups: expected 1 or 2");
-  if (compute_dtype != MICLIP_FP16 && compute_dtype != MICLIP_BF16)
-    return fail(MICLIP_EINVAL, "compute_dtype: expected MICLIP_FP16 or MICLIP_BF16");
-  if (x_dtype != MICLIP_FP16 && x_dtype != MICLIP_F32)
-    return fail(MICLIP_EINVAL, "x_dtype: expected MICLIP_FP16 or MICLIP_F32 (the stream types)");
-  if (act != MICLIP_ACT_QUICKGELU && act != MICLIP_ACT_GELU)
-    return fail(MICLIP_EINVAL, "act: expected MICLIP_ACT_QUICKGELU or MICLIP_ACT_GELU");
-  if (!x) return fail(MICLIP_EINVAL, "null argument: x");
-  if (!labels) return fail(MICLIP_EINVAL, "null argument: labels");
-  if (!text_weights) return fail(MICLIP_EINVAL, "null argument: text_weights");
-  if (!params) return fail(MICLIP_EINVAL, "null argument: params");
-  if (!grads) return fail(MICLIP_EINVAL, "null argument: grads");
-  if (!scratch) return fail(MICLIP_EINVAL, "null argument: scratch");
-  if (!stats) return fail(MICLIP_EINVAL, "null argument: stats");
-  if ((uintptr_t)scratch & 255) return fail(MICLIP_EINVAL, "scratch: expected 256-byte alignment");
+  if (!ft_grad_args_ok("x", x, x_dtype, labels, text_weights, params, B, N, W, E, C, head_dim, act,
+                       compute_dtype, groups, grads, scratch, stats, why))
+    return fail(MICLIP_EINVAL, why);
   MICLIP_HIP(ft_grad(compute_dtype, x_dtype == MICLIP_FP16 ? kF16 : kIn32, x, labels,
                      text_weights, params, B, N, W, E, C, head_dim,
                      act == MICLIP_ACT_GELU ? ACT_GELU : ACT_QUICKGELU, scale, groups, grads,
                      scratch, stats, feats, (hipStream_t)stream));
+  return 0;
+}
+
+int64_t miclip_ft_rows_scratch_bytes(int32_t B, int32_t N, int32_t W, int32_t E, int32_t C,
+                                     int32_t head_dim) {
+  return (int64_t)ft_rows_scratch_bytes(B, N, W, E, C, head_dim);
+}
+
+int miclip_ft_grad_rows(const void* x_cache, int32_t x_dtype, int64_t cache_images,
+                        const int64_t* rows, const int64_t* labels, const float* text_weights,
+                        const float* params, int32_t B, int32_t N, int32_t W, int32_t E, int32_t C,
+                        int32_t head_dim, int32_t act, int32_t compute_dtype, float scale,
+                        int32_t groups, float* grads, void* scratch, float* stats, float* feats,
+                        void* stream) {
+  std::string why;
+  if (!ft_grad_args_ok("x_cache", x_cache, x_dtype, labels, text_weights, params, B, N, W, E, C,
+                       head_dim, act, compute_dtype, groups, grads, scratch, stats, why))
+    return fail(MICLIP_EINVAL, why);
+  if (cache_images < 1) return fail(MICLIP_EINVAL, "cache_images: expected cache_images >= 1");
+  if (!ft_rows_shape_ok(cache_images, B, N, W, E, C, head_dim))
+    return fail(MICLIP_EINVAL, "cache_images: cache_images * N * W reaches 2^47");
+  if (!rows) return fail(MICLIP_EINVAL, "null argument: rows");
+  for (int32_t b = 0; b < B; ++b)
+    if (rows[b] < 0 || rows[b] >= cache_images)
+      return fail(MICLIP_EINVAL, "rows: rows[" + std::to_string(b) + "] = " +
+                                     std::to_string(rows[b]) + " is outside [0, cache_images = " +
+                                     std::to_string(cache_images) + ")");
+  MICLIP_HIP(ft_grad_rows(compute_dtype, x_dtype == MICLIP_FP16 ? kF16 : kIn32, x_cache,
+                          cache_images, rows, labels, text_weights, params, B, N, W, E, C, head_dim,
+                          act == MICLIP_ACT_GELU ? ACT_GELU : ACT_QUICKGELU, scale, groups, grads,
+                          scratch, stats, feats, (hipStream_t)stream));
   return 0;
 }
 

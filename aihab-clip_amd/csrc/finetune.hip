@@ -27,6 +27,10 @@
 //     attention forward (keeping p) and backward (packed dQKV), activation forward /
 //     backward, chunked column sums, casts of the fp32 masters, and the closed-form
 //     gradients of W_in / ln_1 from G = dQKV^T . xhat.
+//   * ft_grad_rows: the same step on images picked out of a cache of trunk outputs. The
+//     only two readers of x (ft_ln_fwd_kernel, ft_add_rows_kernel) take a row map, null
+//     for ft_grad, so the batch is never gathered into a buffer of its own; the host's
+//     indices are checked, then staged from the arguments of ft_stage_rows_kernel.
 //
 // Determinism: every accumulation runs in ascending row order inside one wave,
 // slices are added in index order, there are no atomics; the maximum behind the
@@ -376,17 +380,26 @@ MICLIP_DEV float block_max(float v, float* red) {
 
 constexpr int kLnMaxPer = 8;   // D <= 2048 on 256 threads
 
-// LayerNorm of row r (at x + r * stride elements), eps 1e-5, two-pass fp32 statistics.
-// Any of the outputs may be null: xhat_t / h_t in the compute dtype, xhat_f / h_f fp32,
-// rstd [R].
+// Source row of output row r = b * N + t under a row map: token t of image rows[b] of a
+// cache of N-row blocks; the identity without a map.
+MICLIP_DEV size_t ft_src_row(const int64_t* __restrict__ rows, size_t r, int N) {
+  if (!rows) return r;
+  const size_t b = r / (size_t)N;
+  return (size_t)rows[b] * N + (r - b * N);
+}
+
+// LayerNorm of row r (read at x + ft_src_row(rows, r, N) * stride elements, written at
+// row r), eps 1e-5, two-pass fp32 statistics. Any of the outputs may be null: xhat_t /
+// h_t in the compute dtype, xhat_f / h_f fp32, rstd [R].
 template <typename TI, typename T>
 __global__ __launch_bounds__(256) void ft_ln_fwd_kernel(
-    const TI* __restrict__ x, size_t stride, const float* __restrict__ gamma,
-    const float* __restrict__ beta, T* __restrict__ xhat_t, T* __restrict__ h_t,
-    float* __restrict__ xhat_f, float* __restrict__ h_f, float* __restrict__ rstd_out, int D) {
+    const TI* __restrict__ x, size_t stride, const int64_t* __restrict__ rows, int N,
+    const float* __restrict__ gamma, const float* __restrict__ beta, T* __restrict__ xhat_t,
+    T* __restrict__ h_t, float* __restrict__ xhat_f, float* __restrict__ h_f,
+    float* __restrict__ rstd_out, int D) {
   __shared__ float red[4];
   const size_t r = blockIdx.x;
-  const TI* xr = x + r * stride;
+  const TI* xr = x + ft_src_row(rows, r, N) * stride;
   float v[kLnMaxPer];
   float s = 0.f;
 #pragma unroll
@@ -601,15 +614,29 @@ __global__ __launch_bounds__(256) void ft_act_bwd_kernel(const float* __restrict
   if (e < numel) du[e] = da[e] * *mult * act_grad(u[e], act);
 }
 
-// out[b, k] = a[b, k] + x[b * stride + k] (the residual around the attention, CLS rows)
+// out[b, k] = a[b, k] + x[i * stride + k], i = rows[b] under a row map and b without one
+// (the residual around the attention, CLS rows)
 template <typename TI>
 __global__ __launch_bounds__(256) void ft_add_rows_kernel(const float* __restrict__ a,
                                                           const TI* __restrict__ x, size_t stride,
+                                                          const int64_t* __restrict__ rows,
                                                           float* __restrict__ out, int B, int D) {
   const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (e >= (size_t)B * D) return;
   const size_t b = e / D, k = e - b * D;
-  out[e] = a[e] + to_f<TI>(x[b * stride + k]);
+  const size_t i = rows ? (size_t)rows[b] : b;
+  out[e] = a[e] + to_f<TI>(x[i * stride + k]);
+}
+
+// dst[i] = c.v[i], i < n: a piece of a host array, carried by the launch's own arguments
+constexpr int kStageChunk = 256;
+struct FtRowChunk {
+  int64_t v[kStageChunk];
+};
+__global__ __launch_bounds__(kStageChunk) void ft_stage_rows_kernel(FtRowChunk c,
+                                                                    int64_t* __restrict__ dst,
+                                                                    int n) {
+  if ((int)threadIdx.x < n) dst[threadIdx.x] = c.v[threadIdx.x];
 }
 
 __global__ __launch_bounds__(256) void ft_add_kernel(const float* __restrict__ a,
@@ -793,7 +820,8 @@ void cast_scaled(const float* in, void* out, size_t numel, float* sc, float* par
   } while (0)
 
 template <typename T, typename TI>
-hipError_t ft_grad_t(int dtype, const TI* x, const int64_t* labels, const float* tw,
+hipError_t ft_grad_t(int dtype, const TI* x, const int64_t* rows, const int64_t* labels,
+                     const float* tw,
                      const float* P, int B, int N, int W, int E, int C, int dh, int act,
                      float scale, int groups, float* grads, char* base, float* stats,
                      float* y_out, hipStream_t s) {
@@ -823,17 +851,18 @@ hipError_t ft_grad_t(int dtype, const TI* x, const int64_t* labels, const float*
                      4 * w2, (const float*)nullptr);
 
   // ---- forward ----
-  hipLaunchKernelGGL((ft_ln_fwd_kernel<TI, T>), dim3(M), dim3(256), 0, s, x, (size_t)W, ln1g, ln1b,
-                     Tp(L.xhat), Tp(L.h), (float*)nullptr, (float*)nullptr, (float*)nullptr, W);
+  hipLaunchKernelGGL((ft_ln_fwd_kernel<TI, T>), dim3(M), dim3(256), 0, s, x, (size_t)W, rows, N,
+                     ln1g, ln1b, Tp(L.xhat), Tp(L.h), (float*)nullptr, (float*)nullptr,
+                     (float*)nullptr, W);
   FT_TRY(gemm_store(dtype, Tp(L.h), Tp(L.win), bin, Tp(L.qkv), M, 3 * W, W, ACT_NONE, s));
   hipLaunchKernelGGL(ft_attn_fwd_kernel<T>, dim3(B, H), dim3(256), 0, s, Tp(L.qkv), Tp(L.o),
                      F(L.p), N, W, dh, inv_sqrt);
   FT_TRY(gemm_f32(dtype, Tp(L.o), Tp(L.wo), bo, F(L.tmp), B, W, W, s));
   hipLaunchKernelGGL(ft_add_rows_kernel<TI>, dim3(nblk(bw)), dim3(256), 0, s, F(L.tmp), x,
-                     (size_t)N * W, F(L.x1), B, W);
+                     (size_t)N * W, rows, F(L.x1), B, W);
   hipLaunchKernelGGL((ft_ln_fwd_kernel<float, T>), dim3(B), dim3(256), 0, s, F(L.x1), (size_t)W,
-                     ln2g, ln2b, (T*)nullptr, Tp(L.h2), F(L.xhat2), (float*)nullptr, F(L.rstd2),
-                     W);
+                     (const int64_t*)nullptr, 1, ln2g, ln2b, (T*)nullptr, Tp(L.h2), F(L.xhat2),
+                     (float*)nullptr, F(L.rstd2), W);
   FT_TRY(gemm_f32(dtype, Tp(L.h2), Tp(L.wfc), bfc, F(L.u), B, 4 * W, W, s));
   hipLaunchKernelGGL(ft_act_fwd_kernel<T>, dim3(nblk(4 * bw)), dim3(256), 0, s, F(L.u), Tp(L.a),
                      4 * bw, act);
@@ -841,7 +870,8 @@ hipError_t ft_grad_t(int dtype, const TI* x, const int64_t* labels, const float*
   hipLaunchKernelGGL(ft_add_kernel, dim3(nblk(bw)), dim3(256), 0, s, F(L.tmp), F(L.x1), F(L.x2),
                      bw);
   hipLaunchKernelGGL((ft_ln_fwd_kernel<float, T>), dim3(B), dim3(256), 0, s, F(L.x2), (size_t)W,
-                     lnpg, lnpb, (T*)nullptr, (T*)nullptr, F(L.xhat3), F(L.y), F(L.rstd3), W);
+                     (const int64_t*)nullptr, 1, lnpg, lnpb, (T*)nullptr, (T*)nullptr, F(L.xhat3),
+                     F(L.y), F(L.rstd3), W);
   if (y_out)
     FT_TRY(hipMemcpyAsync(y_out, F(L.y), bw * 4, hipMemcpyDeviceToDevice, s));
 
@@ -913,23 +943,68 @@ hipError_t ft_grad_t(int dtype, const TI* x, const int64_t* labels, const float*
 
 }  // namespace
 
-hipError_t ft_grad(int dtype, int x_dtype, const void* x, const int64_t* labels, const float* tw,
-                   const float* params, int B, int N, int W, int E, int C, int dh, int act,
-                   float scale, int groups, float* grads, void* scratch, float* stats,
-                   float* y_out, hipStream_t s) {
+// rows (device, nullable): the row map of ft_grad_rows; null reads x as it lies
+static hipError_t ft_grad_any(int dtype, int x_dtype, const void* x, const int64_t* rows,
+                              const int64_t* labels, const float* tw, const float* params, int B,
+                              int N, int W, int E, int C, int dh, int act, float scale, int groups,
+                              float* grads, void* scratch, float* stats, float* y_out,
+                              hipStream_t s) {
   if (!ft_shape_ok(B, N, W, E, C, dh) || (dtype != kF16 && dtype != kBF16) ||
       (x_dtype != kF16 && x_dtype != kIn32) || (act != ACT_QUICKGELU && act != ACT_GELU) ||
       (groups != 1 && groups != 2) || ((uintptr_t)scratch & 255))
     return hipErrorInvalidValue;
   char* base = (char*)scratch;
-#define FT_CALL(T, TI)                                                                        \
-  return ft_grad_t<T, TI>(dtype, (const TI*)x, labels, tw, params, B, N, W, E, C, dh, act,   \
-                          scale, groups, grads, base, stats, y_out, s)
+#define FT_CALL(T, TI)                                                                         \
+  return ft_grad_t<T, TI>(dtype, (const TI*)x, rows, labels, tw, params, B, N, W, E, C, dh,   \
+                          act, scale, groups, grads, base, stats, y_out, s)
   if (dtype == kF16 && x_dtype == kF16) FT_CALL(_Float16, _Float16);
   if (dtype == kF16) FT_CALL(_Float16, float);
   if (x_dtype == kF16) FT_CALL(__bf16, _Float16);
   FT_CALL(__bf16, float);
 #undef FT_CALL
+}
+
+hipError_t ft_grad(int dtype, int x_dtype, const void* x, const int64_t* labels, const float* tw,
+                   const float* params, int B, int N, int W, int E, int C, int dh, int act,
+                   float scale, int groups, float* grads, void* scratch, float* stats,
+                   float* y_out, hipStream_t s) {
+  return ft_grad_any(dtype, x_dtype, x, nullptr, labels, tw, params, B, N, W, E, C, dh, act, scale,
+                     groups, grads, scratch, stats, y_out, s);
+}
+
+bool ft_rows_shape_ok(int64_t cache_images, int64_t B, int64_t N, int64_t W, int64_t E, int64_t C,
+                      int64_t dh) {
+  return ft_shape_ok(B, N, W, E, C, dh) && cache_images >= 1 &&
+         cache_images <= (((int64_t)1 << 47) - 1) / (N * W);
+}
+
+size_t ft_rows_scratch_bytes(int B, int N, int W, int E, int C, int dh) {
+  const size_t base = ft_scratch_bytes(B, N, W, E, C, dh);
+  return base ? base + align256((size_t)B * sizeof(int64_t)) : 0;
+}
+
+hipError_t ft_grad_rows(int dtype, int x_dtype, const void* x_cache, int64_t cache_images,
+                        const int64_t* rows_host, const int64_t* labels, const float* tw,
+                        const float* params, int B, int N, int W, int E, int C, int dh, int act,
+                        float scale, int groups, float* grads, void* scratch, float* stats,
+                        float* y_out, hipStream_t s) {
+  if (!ft_rows_shape_ok(cache_images, B, N, W, E, C, dh) || !rows_host || !scratch ||
+      ((uintptr_t)scratch & 255))
+    return hipErrorInvalidValue;
+  for (int b = 0; b < B; ++b)   // before any launch: no kernel sees an index outside the cache
+    if (rows_host[b] < 0 || rows_host[b] >= cache_images) return hipErrorInvalidValue;
+  // the index area follows ft_grad's own scratch; each piece travels as launch arguments, so
+  // the caller's array is free on return and the stream is never waited for
+  int64_t* rows = (int64_t*)((char*)scratch + ft_scratch_bytes(B, N, W, E, C, dh));
+  for (int b0 = 0; b0 < B; b0 += kStageChunk) {
+    const int n = B - b0 < kStageChunk ? B - b0 : kStageChunk;
+    FtRowChunk c;
+    for (int i = 0; i < kStageChunk; ++i) c.v[i] = i < n ? rows_host[b0 + i] : 0;
+    hipLaunchKernelGGL(ft_stage_rows_kernel, dim3(1), dim3(kStageChunk), 0, s, c, rows + b0, n);
+  }
+  FT_TRY(hipGetLastError());
+  return ft_grad_any(dtype, x_dtype, x_cache, rows, labels, tw, params, B, N, W, E, C, dh, act,
+                     scale, groups, grads, scratch, stats, y_out, s);
 }
 
 }  // namespace miclip

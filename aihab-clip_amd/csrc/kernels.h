@@ -267,6 +267,21 @@ hipError_t ft_grad(int dtype, int x_dtype, const void* x, const int64_t* labels,
                    const float* params, int B, int N, int W, int E, int C, int dh, int act,
                    float scale, int groups, float* grads, void* scratch, float* stats,
                    float* y_out, hipStream_t s);
+// ft_grad on the B images whose N-row blocks are x_cache[rows_host[b] * N ..), x_cache
+// [cache_images * N, W]: the two reads of x (ln_1 over the token rows, the CLS residual rows)
+// go through the row map, no gathered copy is formed, every output is bit-identical to
+// ft_grad on a contiguous copy of those blocks. rows_host [B] is a HOST array, checked
+// against [0, cache_images) before any launch and staged behind ft_grad's scratch
+// (ft_rows_scratch_bytes = ft_scratch_bytes + the index area; 0 outside the limits).
+// ft_grad's limits, 1 <= cache_images, cache_images * N * W < 2^47.
+bool ft_rows_shape_ok(int64_t cache_images, int64_t B, int64_t N, int64_t W, int64_t E, int64_t C,
+                      int64_t dh);
+size_t ft_rows_scratch_bytes(int B, int N, int W, int E, int C, int dh);
+hipError_t ft_grad_rows(int dtype, int x_dtype, const void* x_cache, int64_t cache_images,
+                        const int64_t* rows_host, const int64_t* labels, const float* tw,
+                        const float* params, int B, int N, int W, int E, int C, int dh, int act,
+                        float scale, int groups, float* grads, void* scratch, float* stats,
+                        float* y_out, hipStream_t s);
 
 // ---- validation metrics (evaluate.hip), fp32 ----
 // The caller-owned state block, as 8-byte words (include/miclip.h documents it):

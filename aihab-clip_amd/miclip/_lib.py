@@ -51,6 +51,7 @@ EXPORTS = (
     "miclip_gemm_tn_ws_bytes", "miclip_gemm_tn_plan", "miclip_op_gemm_tn", "miclip_ft_adam",
     "miclip_ft_proj_scratch_bytes", "miclip_ft_proj_grad",
     "miclip_encode_image_trunk", "miclip_ft_layout", "miclip_ft_scratch_bytes", "miclip_ft_grad",
+    "miclip_ft_rows_scratch_bytes", "miclip_ft_grad_rows",
     "miclip_eval_state_bytes", "miclip_eval_reset", "miclip_eval_batch",
     "miclip_mx_scale_bytes", "miclip_op_quant_mx", "miclip_op_gemm_mx", "miclip_op_gemm_mx_v", "miclip_op_layernorm_mx",
 )
@@ -189,6 +190,9 @@ def load_library(path: str = None):
         "miclip_ft_scratch_bytes": ([i32, i32, i32, i32, i32, i32], i64),
         "miclip_ft_grad": ([vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, f32, i32,
                             vp, vp, vp, vp, vp], ctypes.c_int),
+        "miclip_ft_rows_scratch_bytes": ([i32, i32, i32, i32, i32, i32], i64),
+        "miclip_ft_grad_rows": ([vp, i32, i64, ctypes.POINTER(i64), vp, vp, vp, i32, i32, i32, i32,
+                                 i32, i32, i32, i32, f32, i32, vp, vp, vp, vp, vp], ctypes.c_int),
         "miclip_eval_state_bytes": ([i32, i32], i64),
         "miclip_eval_reset": ([vp, i32, i32, vp], ctypes.c_int),
         "miclip_eval_batch": ([vp, i32, vp, vp, i32, i32, i32, f32, vp, i32, i32, u32, vp, vp, vp,

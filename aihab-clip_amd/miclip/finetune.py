@@ -27,6 +27,13 @@ Numerics: master parameters, gradients and the Adam state are fp32; GEMM operand
 rounded once (RNE) to the model's compute dtype, gradient operands under a power-of-two
 scale undone in fp32; LayerNorm statistics, softmax, activation derivatives, normalise
 and loss are fp32. No float atomics: a step is bit-identical run to run.
+
+The trunk is a function of the images alone and its weights never change, so with
+`finetune.trunk_cache_views` = V >= 1 it is run once per view before epoch 0 (`TrunkCache`,
+`LastBlockTrainer.fill_view`; what ProLIP's `aug_views` passes of
+`cache_preprojection_features` are to the projector) and every epoch trains on the cached
+residual stream through `miclip_ft_grad_rows`, which reads the cache through a row map
+instead of a gathered copy (`LastBlockTrainer.step_rows`).
 """
 import ctypes
 import math
@@ -38,8 +45,8 @@ import torch
 
 from . import _lib
 from .evaluation import run_validation
-from .feature_cache import (_canonical_backbone_name, _model_device, cache_openclip_embeddings,
-                            prepare_images)
+from .feature_cache import (_canonical_backbone_name, _model_device, _view_sampler,
+                            cache_openclip_embeddings, is_raw_batch, prepare_images, raw_sizes)
 
 ADAM_EPS = 1e-8          # torch.optim.Adam's default, which the reference keeps (:233)
 LOGIT_SCALE = 100.0      # :262, logit_scale is ignored by the reference
@@ -97,6 +104,63 @@ def trainable_names(model, unlocked_groups: int, tune_text: bool = False) -> Lis
     return names
 
 
+def cache_order(n: int, seed: int, epoch: int, shuffle: bool = True) -> torch.Tensor:
+    """Order (int64 [n], host) in which an epoch visits the n cached images: a
+    `torch.randperm` under a CPU generator seeded from (seed, epoch), whatever the batch
+    size; ascending when `shuffle` is off."""
+    n = int(n)
+    if not shuffle:
+        return torch.arange(n, dtype=torch.int64)
+    g = torch.Generator(device="cpu")
+    g.manual_seed((int(seed) * 1000003 + int(epoch)) % (1 << 63))
+    return torch.randperm(n, generator=g, dtype=torch.int64)
+
+
+def cache_view(epoch: int, views: int) -> int:
+    """The cached view that epoch `epoch` trains on: views are taken in turn."""
+    return int(epoch) % int(views)
+
+
+def trunk_cache_config(cfg):
+    """(views, shuffle, max_bytes) from cfg["finetune"]: `trunk_cache_views` (0 or absent:
+    no cache), `trunk_cache_shuffle` (True) and `trunk_cache_max_bytes` (None: half of the
+    free device memory when the method starts)."""
+    ft = (cfg.get("finetune") if hasattr(cfg, "get") else None) or {}
+    views = ft.get("trunk_cache_views", 0)
+    views = 0 if views is None else views
+    if isinstance(views, bool) or not isinstance(views, int):
+        raise ValueError(f"finetune.trunk_cache_views must be an integer >= 0, got {views!r}")
+    if views < 0:
+        raise ValueError(f"finetune.trunk_cache_views must be >= 0, got {views}")
+    budget = ft.get("trunk_cache_max_bytes", None)
+    if budget is not None:
+        if isinstance(budget, bool) or not isinstance(budget, int) or budget < 0:
+            raise ValueError(f"finetune.trunk_cache_max_bytes must be an integer >= 0, got "
+                             f"{budget!r}")
+    return views, bool(ft.get("trunk_cache_shuffle", True)), budget
+
+
+class TrunkCache:
+    """The frozen trunk's output for whole passes over a loader. Per view: x [n * N, W] on
+    the device in the handle's stream type (image i's token block is rows i * N .. i * N + N),
+    the targets [n] as int64 on the host (`targets_host`) and on the device (`targets`), and
+    n. `max_bytes` (None: no limit) bounds the bytes of x over all views; `batch_size` is the
+    size of the first batch that was cached."""
+
+    def __init__(self, max_bytes: Optional[int] = None):
+        self.max_bytes = None if max_bytes is None else int(max_bytes)
+        self.x, self.targets, self.targets_host, self.n = [], [], [], []
+        self.batch_size = None
+
+    @property
+    def views(self) -> int:
+        return len(self.x)
+
+    @property
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in self.x)
+
+
 class LastBlockTrainer:
     """Adam on the unlocked tail of `model`'s image tower against fixed `text_weights`
     [E, C]: what :231-234 and the batch loop :247-274 do for one model.
@@ -107,6 +171,11 @@ class LastBlockTrainer:
     synchronisation beyond the range check of host-side labels; set_epoch(e) moves the
     cosine schedule; commit() writes the master parameters into the model, after which
     `encode_image`, `run_validation` and the caches see the tuned model.
+
+    fill_view(cache, loader) runs the trunk once over a loader into a `TrunkCache`;
+    step_rows(cache, view, rows) is step() on cached images, without the trunk
+    (`miclip_ft_grad_rows` reads the cache through the row map), bit-identical to step() on
+    the same images.
     """
 
     def __init__(self, model, text_weights, *, unlocked_groups: int = 1, lr: float,
@@ -251,6 +320,78 @@ class LastBlockTrainer:
         return stats[0], stats[1]
 
     @torch.no_grad()
+    def fill_view(self, cache: TrunkCache, loader, augment=None) -> int:
+        """One pass of `trunk` over `loader`, appended to `cache` as a view; returns the
+        view's index. Raw uint8 batches go through `prepare_images` with the parameters of
+        `augment(sizes, first_row)` (as `compute_image_features`); transformed tensors are
+        stored as the loader yields them. Raises ValueError, leaving the cache as it was,
+        once the cached bytes would pass `cache.max_bytes`. While a view is filled its
+        batches and their concatenation exist side by side."""
+        parts, labels, row, held = [], [], 0, cache.nbytes
+        for images, targets in loader:
+            params = None
+            if augment is not None and is_raw_batch(images):
+                params = augment(raw_sizes(images), row)
+            img = prepare_images(self.model, images, self.device, params)
+            B = int(img.shape[0])
+            lab = self._labels(targets, B)
+            held += B * self.N * self.W * (torch.finfo(self.x_dtype).bits // 8)
+            if cache.max_bytes is not None and held > cache.max_bytes:
+                raise ValueError(
+                    f"trunk cache: view {cache.views} needs {held} bytes after {row + B} images, "
+                    f"over the budget of {cache.max_bytes} bytes (finetune.trunk_cache_max_bytes)")
+            parts.append(self.trunk(img).clone())
+            labels.append(lab)
+            row += B
+        if not parts:
+            raise ValueError("Empty inputs: the loader yielded no batch.")
+        if cache.batch_size is None:
+            cache.batch_size = int(labels[0].numel())
+        lab = torch.cat(labels)
+        cache.x.append(torch.cat(parts) if len(parts) > 1 else parts[0])
+        cache.targets.append(lab)
+        cache.targets_host.append(lab.cpu())
+        cache.n.append(row)
+        return cache.views - 1
+
+    @torch.no_grad()
+    def grad_rows(self, cache: TrunkCache, view: int, rows, labels=None, feats=None):
+        """`grad` for the cached images `rows` (host indices into view `view`, repeats
+        allowed), read in place through `miclip_ft_grad_rows`. `labels` (optional, device
+        int64 [B]) spares the gather of the view's targets."""
+        idx = torch.as_tensor(rows, dtype=torch.int64, device="cpu").reshape(-1).contiguous()
+        B, n, x = int(idx.numel()), cache.n[view], cache.x[view]
+        if B < 1:
+            raise ValueError("Empty inputs: rows has no index.")
+        if int(idx.min()) < 0 or int(idx.max()) >= n:
+            raise ValueError(f"rows must lie in [0, {n}); got [{int(idx.min())}, {int(idx.max())}].")
+        if labels is None:
+            labels = cache.targets[view][idx.to(self.device)]
+        need = self.lib.miclip_ft_rows_scratch_bytes(B, self.N, self.W, self.E, self.C, self.dh)
+        if need <= 0:
+            raise ValueError(f"unsupported batch size {B}")
+        if self._scratch is None or self._scratch.numel() < need:
+            self._scratch = torch.empty(need, device=self.device, dtype=torch.uint8)
+        stats = torch.empty(2, device=self.device, dtype=torch.float32)
+        xdt = _lib.MICLIP_FP16 if x.dtype == torch.float16 else _lib.MICLIP_F32
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.miclip_ft_grad_rows(
+                _ptr(x), xdt, n, ctypes.cast(idx.data_ptr(), ctypes.POINTER(ctypes.c_int64)),
+                _ptr(labels), _ptr(self.text_weights), _ptr(self.params), B, self.N, self.W,
+                self.E, self.C, self.dh, self.act, self.dtype, LOGIT_SCALE, self.unlocked_groups,
+                _ptr(self.grads), _ptr(self._scratch), _ptr(stats),
+                _ptr(feats) if feats is not None else None, _lib.stream_handle(self.device)),
+                "miclip_ft_grad_rows")
+        return stats
+
+    @torch.no_grad()
+    def step_rows(self, cache: TrunkCache, view: int, rows, labels=None):
+        """`step` on the cached images `rows` of view `view`: no trunk."""
+        stats = self.grad_rows(cache, view, rows, labels)
+        self.adam()
+        return stats[0], stats[1]
+
+    @torch.no_grad()
     def features(self, images, normalize=True):
         """Embeddings [B, E] of `images` under the master parameters (before commit())."""
         x = self.trunk(images)
@@ -374,6 +515,7 @@ class FTOpenCLIP:
                 shots, config_file, return_valid, prompt_tokens=None, num_templates=None):
         cfg = self.cfg
         groups, tune_text, lr, epochs, val_interval = validate_config(cfg, model)
+        views, shuffle, budget = trunk_cache_config(cfg)
         ft_cfg = cfg["finetune"] or {}
         if getattr(model, "surface", None) != "open_clip":
             raise ValueError("FTOpenCLIP needs a model on the open_clip surface (encode_image "
@@ -399,6 +541,15 @@ class FTOpenCLIP:
 
         trainer = LastBlockTrainer(model, text_weights, unlocked_groups=groups, lr=lr, epochs=epochs)
         self.trainer = trainer
+        cache = None
+        if views:   # the frozen trunk, once per view (ProLIP's aug_views passes)
+            if budget is None:
+                budget = torch.cuda.mem_get_info(device)[0] // 2
+            cache = TrunkCache(budget)
+            for v in range(views):
+                trainer.fill_view(cache, train_loader, _view_sampler(cfg, model, v))
+        self.trunk_cache = cache
+        seed = int(cfg.get("seed", 1) or 1)
         val = (None,) * 6
         print("\nStart Training procedure")
         for e in range(epochs):
@@ -406,13 +557,26 @@ class FTOpenCLIP:
             trainer.set_epoch(e)
             acc = torch.zeros(2, device=device, dtype=torch.float32)   # sum of batch-mean CE, correct
             seen = batches = 0
-            for images, targets in train_loader:
-                x = prepare_images(model, images, device)
-                loss_sum, correct = trainer.step(x, targets)
-                acc[0] += loss_sum / x.shape[0]
-                acc[1] += correct
-                seen += int(x.shape[0])
-                batches += 1
+            if cache is None:
+                for images, targets in train_loader:
+                    x = prepare_images(model, images, device)
+                    loss_sum, correct = trainer.step(x, targets)
+                    acc[0] += loss_sum / x.shape[0]
+                    acc[1] += correct
+                    seen += int(x.shape[0])
+                    batches += 1
+            else:
+                view = cache_view(e, views)
+                order = cache_order(cache.n[view], seed, e, shuffle)
+                labels = cache.targets[view][order.to(device)]    # the epoch's one upload
+                for lo in range(0, cache.n[view], cache.batch_size):
+                    rows = order[lo:lo + cache.batch_size]
+                    B = int(rows.numel())
+                    loss_sum, correct = trainer.step_rows(cache, view, rows, labels[lo:lo + B])
+                    acc[0] += loss_sum / B
+                    acc[1] += correct
+                    seen += B
+                    batches += 1
             run_loss, hits = acc.tolist()                              # the epoch's one host read
             print("Acc: {:.4f} ({:}/{:}), Avg Loss: {:.4f}, LR: {:.2e}".format(
                 hits / max(seen, 1), hits, seen, run_loss / max(batches, 1), trainer.lr))

@@ -459,6 +459,30 @@ int miclip_ft_grad(const void* x, int32_t x_dtype, const int64_t* labels,
                    int32_t W, int32_t E, int32_t C, int32_t head_dim, int32_t act,
                    int32_t compute_dtype, float scale, int32_t groups, float* grads,
                    void* scratch, float* stats, float* feats, void* stream);
+/* miclip_ft_grad_rows is miclip_ft_grad on the B images whose token blocks are
+ * x_cache[rows[b] * N .. rows[b] * N + N), x_cache [cache_images * N, W] in
+ * x_dtype as miclip_encode_image_trunk wrote it: the frozen trunk encoded once
+ * per augmentation view (as ProLIP's cache_preprojection_features does for the
+ * projector) and every epoch trained from the cached rows. The two reads of x
+ * -- ln_1 over the token rows and the CLS residual rows -- go through the row
+ * map; no gathered [B * N, W] copy is formed, and grads, stats and feats are
+ * bit-identical to miclip_ft_grad on a contiguous copy of those blocks. An
+ * image may appear more than once. rows [B] is a HOST array: every index is
+ * checked against [0, cache_images) before any launch (MICLIP_EINVAL names
+ * `rows`), then staged into the scratch by the launches' own arguments, so the
+ * array is free on return, nothing is allocated and the stream is not waited
+ * for. Limits: those of miclip_ft_grad, 1 <= cache_images and cache_images * N
+ * * W < 2^47; scratch is miclip_ft_rows_scratch_bytes bytes
+ * (miclip_ft_scratch_bytes plus the index area; 0 outside the limits), 256-byte
+ * aligned. */
+int64_t miclip_ft_rows_scratch_bytes(int32_t B, int32_t N, int32_t W, int32_t E, int32_t C,
+                                     int32_t head_dim);
+int miclip_ft_grad_rows(const void* x_cache, int32_t x_dtype, int64_t cache_images,
+                        const int64_t* rows /* HOST [B] */, const int64_t* labels,
+                        const float* text_weights, const float* params, int32_t B, int32_t N,
+                        int32_t W, int32_t E, int32_t C, int32_t head_dim, int32_t act,
+                        int32_t compute_dtype, float scale, int32_t groups, float* grads,
+                        void* scratch, float* stats, float* feats, void* stream);
 
 /* ---- validation metrics on features or logits, fp32 ----
  * Replace the body of _run_validation's batch loop (methods/PEFT_openclip.py:
