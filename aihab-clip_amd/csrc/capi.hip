@@ -1200,6 +1200,103 @@ int miclip_prolip_adam(const void* x, int32_t x_dtype, const float* dZ, int32_t 
   return 0;
 }
 
+// ---- Tip-Adapter cache classifier (tip.hip) ----
+// The limits are tip_bad_arg's (tip.hip); `which` (kTip* bits) names the arguments the call
+// has, and the message names the violated one and adds the values that were passed.
+static bool tip_args_ok(unsigned which, int64_t Nq, int64_t Nk, int64_t E, int64_t C, int64_t nb,
+                        int64_t na, std::string& why) {
+  const char* bad = tip_bad_arg(which, Nq, Nk, E, C, nb, na);
+  if (!bad) return true;
+  why = std::string(bad) + ", got";
+  const struct { unsigned bit; const char* name; int64_t v; } args[] = {
+      {kTipNq, "Nq", Nq}, {kTipNk, "Nk", Nk}, {kTipE, "E", E},
+      {kTipC, "C", C},    {kTipNb, "nb", nb}, {kTipNa, "na", na}};
+  for (const auto& a : args)
+    if (which & a.bit) why += std::string(" ") + a.name + "=" + std::to_string(a.v);
+  return false;
+}
+
+static bool tip_dtype_arg_ok(int32_t dtype, const char* name, std::string& why) {
+  if (dtype != MICLIP_F32 && dtype != MICLIP_FP16 && dtype != MICLIP_BF16)
+    why = std::string(name) + " must be MICLIP_F32, MICLIP_FP16 or MICLIP_BF16, got " +
+          std::to_string(dtype);
+  return why.empty();
+}
+
+int64_t miclip_tip_scratch_bytes(int32_t Nq, int32_t Nk, int32_t E, int32_t C, int32_t nb,
+                                 int32_t na) {
+  return (int64_t)tip_scratch_bytes(Nq, Nk, E, C, nb, na);
+}
+
+int miclip_tip_keys(const void* const* views, int32_t view_dtype, int32_t A, int32_t Nk,
+                    int32_t Wv, int32_t E, const float* proj, float* keys, void* stream) {
+  const std::pair<const void*, const char*> ptrs[] = {{views, "views"}, {proj, "proj"},
+                                                      {keys, "keys"}};
+  for (const auto& a : ptrs)
+    if (!a.first) return fail(MICLIP_EINVAL, std::string("null argument: ") + a.second);
+  std::string why;
+  if (!tip_dtype_arg_ok(view_dtype, "view_dtype", why)) return fail(MICLIP_EINVAL, why);
+  if (A < 1 || A > 1024) return fail(MICLIP_EINVAL, "A must be in 1..1024, got " + std::to_string(A));
+  if (!tip_args_ok(kTipNk | kTipE, 0, Nk, E, 0, 0, 0, why)) return fail(MICLIP_EINVAL, why);
+  if (Wv < 16 || Wv > 65536 || Wv % 16)
+    return fail(MICLIP_EINVAL, "Wv must be a multiple of 16 in 16..65536, got " + std::to_string(Wv));
+  if (((uintptr_t)views & 7) || ((uintptr_t)proj & 15) || ((uintptr_t)keys & 15))
+    return fail(MICLIP_EINVAL,
+                "views / proj / keys: expected an 8-byte aligned pointer array and 16-byte "
+                "aligned proj and keys");
+  MICLIP_HIP(tip_keys(view_dtype, views, A, proj, keys, Nk, Wv, E, (hipStream_t)stream));
+  return 0;
+}
+
+int miclip_tip_affinity(const void* F, int32_t f_dtype, const float* keys, int32_t Nq, int32_t Nk,
+                        int32_t E, float scale, float* affinity, void* stream) {
+  const std::pair<const void*, const char*> ptrs[] = {{F, "F"}, {keys, "keys"},
+                                                      {affinity, "affinity"}};
+  for (const auto& a : ptrs)
+    if (!a.first) return fail(MICLIP_EINVAL, std::string("null argument: ") + a.second);
+  std::string why;
+  if (!tip_dtype_arg_ok(f_dtype, "f_dtype", why)) return fail(MICLIP_EINVAL, why);
+  if (!tip_args_ok(kTipNq | kTipNk | kTipE, Nq, Nk, E, 0, 0, 0, why)) return fail(MICLIP_EINVAL, why);
+  if (((uintptr_t)F & 15) || ((uintptr_t)keys & 15))
+    return fail(MICLIP_EINVAL, "F / keys: expected 16-byte aligned operands");
+  MICLIP_HIP(tip_affinity(f_dtype, F, keys, affinity, Nq, Nk, E, scale, (hipStream_t)stream));
+  return 0;
+}
+
+int miclip_tip_grid(const float* affinity, const int32_t* key_labels, const float* clip_logits,
+                    const int32_t* labels, const float* betas, const float* alphas, int32_t Nq,
+                    int32_t Nk, int32_t C, int32_t nb, int32_t na, int32_t* correct,
+                    void* scratch, void* stream) {
+  const std::pair<const void*, const char*> ptrs[] = {
+      {affinity, "affinity"}, {key_labels, "key_labels"}, {clip_logits, "clip_logits"},
+      {labels, "labels"}, {betas, "betas"}, {alphas, "alphas"}, {correct, "correct"},
+      {scratch, "scratch"}};
+  for (const auto& a : ptrs)
+    if (!a.first) return fail(MICLIP_EINVAL, std::string("null argument: ") + a.second);
+  std::string why;
+  if (!tip_args_ok(kTipAll & ~kTipE, Nq, Nk, 0, C, nb, na, why)) return fail(MICLIP_EINVAL, why);
+  if ((uintptr_t)scratch & 15) return fail(MICLIP_EINVAL, "scratch: expected a 16-byte aligned pointer");
+  MICLIP_HIP(tip_grid(affinity, key_labels, clip_logits, labels, betas, alphas, correct, Nq, Nk, C,
+                      nb, na, scratch, (hipStream_t)stream));
+  return 0;
+}
+
+int miclip_tip_logits(const float* affinity, const int32_t* key_labels, const float* clip_logits,
+                      int32_t Nq, int32_t Nk, int32_t C, float beta, float alpha, float* logits,
+                      void* scratch, void* stream) {
+  const std::pair<const void*, const char*> ptrs[] = {
+      {affinity, "affinity"}, {key_labels, "key_labels"}, {clip_logits, "clip_logits"},
+      {logits, "logits"}, {scratch, "scratch"}};
+  for (const auto& a : ptrs)
+    if (!a.first) return fail(MICLIP_EINVAL, std::string("null argument: ") + a.second);
+  std::string why;
+  if (!tip_args_ok(kTipNq | kTipNk | kTipC, Nq, Nk, 0, C, 0, 0, why)) return fail(MICLIP_EINVAL, why);
+  if ((uintptr_t)scratch & 15) return fail(MICLIP_EINVAL, "scratch: expected a 16-byte aligned pointer");
+  MICLIP_HIP(tip_logits(affinity, key_labels, clip_logits, beta, alpha, logits, Nq, Nk, C, scratch,
+                        (hipStream_t)stream));
+  return 0;
+}
+
 // ---- last-block fine-tuning (finetune.hip) ----
 static bool gemm_tn_args_ok(int32_t M, int32_t Nn, int32_t K, std::string& why) {
   if (M < 1 || M > 0x7fffffff - 64) why = "M: expected M >= 1";

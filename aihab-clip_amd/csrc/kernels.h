@@ -228,6 +228,40 @@ hipError_t prolip_adam(int x_dtype, const void* x, const float* dZ, const float*
                        int E, int G, float lr_factor, float lambda_div, int step, float eps,
                        hipStream_t s);
 
+// ---- Tip-Adapter cache classifier and (beta, alpha) search (tip.hip), fp32 ----
+// Nq query rows, Nk cache keys, E embedding width, C classes, nb betas, na alphas:
+// 1 <= Nq <= 2^24, 1 <= Nk <= 65536, E % 16 == 0, 16 <= E <= 1024, 1 <= C <= 1024,
+// 1 <= nb, na <= 1024, nb * na <= 65536, else hipErrorInvalidValue. tip_bad_arg is the
+// one statement of these limits: the first violated one as "<argument> must ...", or
+// null. `which` (kTip* bits) says which arguments the call has; the others are not
+// looked at, and every value of a selected argument, negative ones included, is checked.
+enum TipArg : unsigned {
+  kTipNq = 1, kTipNk = 2, kTipE = 4, kTipC = 8, kTipNb = 16, kTipNa = 32, kTipAll = 63
+};
+const char* tip_bad_arg(unsigned which, int64_t Nq, int64_t Nk, int64_t E, int64_t C, int64_t nb,
+                        int64_t na);
+size_t tip_scratch_bytes(int Nq, int Nk, int E, int C, int nb, int na);   // 0 outside the limits
+// keys [Nk, E] = mean over the A views of normalize(x_v proj), divided by its row norm
+// (a plain division: an all-zero row gives NaN). views: DEVICE array of A device
+// pointers to x_v [Nk, Wv] (x_dtype kIn32 / kF16 / kBF16, 16-B aligned); proj [Wv, E].
+// 1 <= A <= 1024, Wv % 16 == 0, 16 <= Wv <= 65536.
+hipError_t tip_keys(int x_dtype, const void* const* views, int A, const float* proj, float* keys,
+                    int Nk, int Wv, int E, hipStream_t s);
+// aff [Nq, Nk] = scale * F keys^T; F [Nq, E] (f_dtype kIn32 / kF16 / kBF16), keys [Nk, E].
+hipError_t tip_affinity(int f_dtype, const void* F, const float* keys, float* aff, int Nq, int Nk,
+                        int E, float scale, hipStream_t s);
+// correct [nb, na] = rows whose first argmax of Z + alphas[ia] * s(betas[ib]) is their
+// label, s_c(beta) = sum over the keys k of class c of exp(-(beta - beta aff_k)) in
+// ascending k. key_labels [Nk] and labels [Nq] int32 in [0, C); Z [Nq, C].
+hipError_t tip_grid(const float* aff, const int32_t* key_labels, const float* Z,
+                    const int32_t* labels, const float* betas, const float* alphas,
+                    int32_t* correct, int Nq, int Nk, int C, int nb, int na, void* scratch,
+                    hipStream_t s);
+// out [Nq, C] = Z + alpha * s(beta): the numbers tip_grid compares, bit for bit.
+hipError_t tip_logits(const float* aff, const int32_t* key_labels, const float* Z, float beta,
+                      float alpha, float* out, int Nq, int Nk, int C, void* scratch,
+                      hipStream_t s);
+
 // ---- last-block fine-tuning of the image tower (finetune.hip) ----
 // gemm_tn: G [Nn, K] fp32 = sum_m A[m, Nn] * X[m, K] (A, X compute dtype, row-major,
 // 16-B aligned; both contracted along rows), times *out_scale (device, nullable).

@@ -13,7 +13,7 @@ import warnings
 
 import torch
 
-from . import augment, embed_vis, evaluation
+from . import augment, embed_vis, evaluation, tip
 from .augment import build_clip_transforms
 from .configs import (MODEL_CONFIGS, OPEN_CLIP_MODELS, CLIPConfig, available_models,
                       config_from_state_dict)
@@ -23,6 +23,8 @@ from .evaluation import (ClassificationTracker, Evaluator, L2MetricsAccumulator,
                          run_validation)
 from .model import CLIP, build_model
 from .preprocess import Transform
+from .tip import (beta_alpha_lists, build_cache_model, cache_model_from_views, search_hp_tip,
+                  tip_accuracy_grid, tip_logits)
 from .weights import generate_state_dict, synthetic_images
 
 __all__ = ["available_models", "load", "tokenize", "build_model", "CLIP", "CLIPConfig",
@@ -30,7 +32,8 @@ __all__ = ["available_models", "load", "tokenize", "build_model", "CLIP", "CLIPC
            "evaluate_features", "Evaluator", "L2MetricsAccumulator", "ClassificationTracker",
            "aggregate_logits_to_l2", "map_l3_targets_to_l2", "augment",
            "build_clip_transforms", "embed_vis", "tsne", "pca_reduce", "visualize_cache",
-           "TsneResult"]
+           "TsneResult", "tip", "build_cache_model", "cache_model_from_views", "search_hp_tip",
+           "tip_accuracy_grid", "tip_logits", "beta_alpha_lists"]
 
 
 class SeededWeightsWarning(UserWarning):

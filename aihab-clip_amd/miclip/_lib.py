@@ -48,6 +48,8 @@ EXPORTS = (
     "miclip_kmeans_scratch_bytes", "miclip_kmeans_seed", "miclip_kmeans_lloyd",
     "miclip_tsne_scratch_bytes", "miclip_tsne_affinities", "miclip_tsne_run",
     "miclip_prolip_grad", "miclip_prolip_adam",
+    "miclip_tip_scratch_bytes", "miclip_tip_keys", "miclip_tip_affinity", "miclip_tip_grid",
+    "miclip_tip_logits",
     "miclip_gemm_tn_ws_bytes", "miclip_gemm_tn_plan", "miclip_op_gemm_tn", "miclip_ft_adam",
     "miclip_ft_proj_scratch_bytes", "miclip_ft_proj_grad",
     "miclip_encode_image_trunk", "miclip_ft_layout", "miclip_ft_scratch_bytes", "miclip_ft_grad",
@@ -177,6 +179,12 @@ def load_library(path: str = None):
                                ctypes.c_int),
         "miclip_prolip_adam": ([vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, f32, f32,
                                 i32, f32, vp, vp, vp, vp], ctypes.c_int),
+        "miclip_tip_scratch_bytes": ([i32, i32, i32, i32, i32, i32], i64),
+        "miclip_tip_keys": ([vp, i32, i32, i32, i32, i32, vp, vp, vp], ctypes.c_int),
+        "miclip_tip_affinity": ([vp, i32, vp, i32, i32, i32, f32, vp, vp], ctypes.c_int),
+        "miclip_tip_grid": ([vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp],
+                            ctypes.c_int),
+        "miclip_tip_logits": ([vp, vp, vp, i32, i32, i32, f32, f32, vp, vp, vp], ctypes.c_int),
         "miclip_gemm_tn_ws_bytes": ([i32, i32, i32], i64),
         "miclip_gemm_tn_plan": ([i32, i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)],
                                 ctypes.c_int),

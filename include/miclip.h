@@ -372,6 +372,60 @@ int miclip_prolip_adam(const void* x, int32_t x_dtype, const float* dZ, int32_t 
                        int32_t step, float eps, const float* grad_partials, float* mse_partials,
                        float* history, void* stream);
 
+/* ---- Tip-Adapter: training-free cache classifier and its (beta, alpha) search, fp32 ----
+ * methods/utils.py:23-62 (build_cache_model) and :64-94 (search_hp_tip) on the device.
+ * Nq query rows, Nk cache keys, E embedding width, C classes, nb betas, na alphas, A
+ * views of width Wv. Limits: 1 <= Nq <= 2^24, 1 <= Nk <= 65536, E % 16 == 0,
+ * 16 <= E <= 1024, 1 <= C <= 1024, 1 <= nb, na <= 1024, nb * na <= 65536,
+ * 1 <= A <= 1024, Wv % 16 == 0, 16 <= Wv <= 65536, dtypes MICLIP_F32 / MICLIP_FP16 /
+ * MICLIP_BF16 (widened exactly in the load), no NULL pointer; anything else is
+ * MICLIP_EINVAL with the argument named in miclip_last_error, before any launch. No
+ * model handle is needed. All pointers are caller-owned device memory, F, keys, proj and
+ * every view 16-byte aligned (checked, except the view pointers: they live in device
+ * memory and are trusted), the `views` array 8-byte aligned; the calls are stream-ordered, never synchronise and
+ * never allocate. All arithmetic is fp32; there are no float atomics and every float
+ * sum has a fixed shape, so results are bit-identical run to run.
+ * key_labels [Nk] and labels [Nq] are int32 in [0, C): host callers check that before
+ * the call (miclip/tip.py does); the entries trust device labels, and a label outside
+ * the range reads or writes nothing out of bounds (such a key belongs to no class,
+ * such a row is never counted correct).
+ * scratch: miclip_tip_scratch_bytes(Nq, Nk, E, C, nb, na) bytes (0 outside the limits),
+ * 16-byte aligned, used by miclip_tip_grid and miclip_tip_logits. */
+int64_t miclip_tip_scratch_bytes(int32_t Nq, int32_t Nk, int32_t E, int32_t C, int32_t nb,
+                                 int32_t na);
+/* miclip_tip_keys replaces methods/utils.py:37-48: views is a DEVICE array of A device
+ * pointers to the cached pre-projection views x_v [Nk, Wv] (f{v}.pth), proj [Wv, E]
+ * fp32. Per view f_v = F.normalize(x_v @ proj) (eps 1e-12, :38-39); keys [Nk, E] = the
+ * mean over the views, summed in ascending v (:47), divided by its row norm (:48). That
+ * last step is a plain division as in the reference: a row whose mean is all zero
+ * yields a non-finite key. The permute of :49 is left to the caller. */
+int miclip_tip_keys(const void* const* views, int32_t view_dtype, int32_t A, int32_t Nk,
+                    int32_t Wv, int32_t E, const float* proj, float* keys, void* stream);
+/* miclip_tip_affinity replaces methods/utils.py:79: affinity [Nq, Nk] = scale *
+ * F [Nq, E] @ keys [Nk, E]^T (scale 1 for the affinity). With keys = clip_weights^T
+ * [C, E] and scale 100 it gives the clip_logits of :82. */
+int miclip_tip_affinity(const void* F, int32_t f_dtype, const float* keys, int32_t Nq, int32_t Nk,
+                        int32_t E, float scale, float* affinity, void* stream);
+/* miclip_tip_grid replaces the double loop of methods/utils.py:74-90 (with cls_acc,
+ * :16-21) up to the choice of the best pair: correct [nb, na] (int32, overwritten) =
+ * the number of rows whose first argmax over c of clip_logits[c] + alphas[ia] *
+ * s_c(betas[ib]) equals their label, where s_c(beta) = sum over the keys k with
+ * key_labels[k] == c, in ascending k, of exp(-(beta - beta * affinity[k])) -- :81's
+ * product with the one-hot cache_values; a class with no key contributes 0. NaN ranks
+ * above every number and the lower index wins ties (torch.topk). affinity [Nq, Nk] is
+ * miclip_tip_affinity's or a caller's adapter(features) (:76-77); clip_logits [Nq, C];
+ * betas [nb], alphas [na] fp32. One exp per (row, key, beta); nothing of size
+ * Nq * nb * C is formed. */
+int miclip_tip_grid(const float* affinity, const int32_t* key_labels, const float* clip_logits,
+                    const int32_t* labels, const float* betas, const float* alphas, int32_t Nq,
+                    int32_t Nk, int32_t C, int32_t nb, int32_t na, int32_t* correct,
+                    void* scratch, void* stream);
+/* miclip_tip_logits replaces methods/utils.py:81-83 for one pair: logits [Nq, C] =
+ * clip_logits + alpha * s(beta), bit for bit the numbers miclip_tip_grid compares. */
+int miclip_tip_logits(const float* affinity, const int32_t* key_labels, const float* clip_logits,
+                      int32_t Nq, int32_t Nk, int32_t C, float beta, float alpha, float* logits,
+                      void* scratch, void* stream);
+
 /* ---- fine-tuning of the image tower's tail ----
  * FTOpenCLIP's training step (methods/PEFT_openclip.py:247-274) for
  * unlocked_groups 1 and 2 of lock_image_tower (:196-197): first the op-level
