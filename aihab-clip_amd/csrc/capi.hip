@@ -1669,6 +1669,35 @@ int miclip_op_layernorm(int32_t dtype, const void* in, const float* gamma, const
   return 0;
 }
 
+int miclip_op_layernorm_rows(int32_t dtype, const void* in, const int32_t* rows,
+                             int32_t in_stride_rows, const float* gamma, const float* beta,
+                             void* out, int32_t flags, int32_t R, int32_t D, void* stream) {
+  if (!in || !gamma || !beta || !out) return fail(MICLIP_EINVAL, "null argument");
+  if (!rows && in_stride_rows < 1) return fail(MICLIP_EINVAL, "row stride must be >= 1");
+  const bool of32 = flags & 1;
+  MICLIP_HIP(layernorm(dtype, in, rows, in_stride_rows, gamma, beta, of32 ? (float*)out : nullptr,
+                       of32 ? nullptr : out, R, D, (flags >> 2) & 1, (hipStream_t)stream,
+                       (flags >> 1) & 1));
+  return 0;
+}
+
+int miclip_op_gemm_patch(int32_t dtype, const void* A, const void* W, const float* pos, void* X,
+                         int32_t M, int32_t N, int32_t K, int32_t np, int32_t resid16,
+                         int32_t variant, void* stream) {
+  if (!A || !W || !pos || !X) return fail(MICLIP_EINVAL, "null argument");
+  MICLIP_HIP(gemm_patch(dtype, A, W, pos, X, M, N, K, np, (hipStream_t)stream, resid16 != 0,
+                        variant));
+  return 0;
+}
+
+int miclip_op_class_token(const float* cls, const float* pos, void* X, int32_t B, int32_t ntok,
+                          int32_t D, int32_t resid16, void* stream) {
+  if (!cls || !pos || !X) return fail(MICLIP_EINVAL, "null argument");
+  if (B < 1 || ntok < 1 || D < 1) return fail(MICLIP_EINVAL, "B, ntok and D must be >= 1");
+  MICLIP_HIP(class_token(cls, pos, X, B, ntok, D, (hipStream_t)stream, resid16 != 0));
+  return 0;
+}
+
 int miclip_op_attention(int32_t dtype, const void* qkv, void* out, int32_t B, int32_t N,
                         int32_t H, int32_t head_dim, int32_t causal, int32_t variant,
                         void* stream) {

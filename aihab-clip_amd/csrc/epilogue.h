@@ -49,6 +49,14 @@ MICLIP_DEV float4 ld_bias4_nb(const float* b, int col) {
 // the exponent, and erfc(-z) = 2 - erfc(z) for v >= 0. 19 VALU ops against
 // ~40 for libm erff, and no 1 + erf cancellation in the negative tail (CPU
 // check: max abs error 2.4e-7, max rel 5e-6 against double erfc on [-12, 12]).
+// On the device (tests/test_gpu_gemm_exact.py, every fp16 v with |v| <= 16 and the
+// integer-grid cases): every output is the rounding of a value within 2e-5 relative
+// of the float64 GELU. v_exp_f32 and v_rcp_f32 flush a subnormal RESULT to zero, so
+// the value is -0 as soon as the factor e = 2^(...) here, or 1 / (1 + 2^t) in
+// QuickGELU, drops below 2^-126, while its exact product with v t (|v t| < 2.83),
+// resp. v, is still a normal fp32: GELU for v in about (-13.15, -13.06), QuickGELU for
+// v in about (-53.7, -51.3), exact |y| <= 6.4e-37. An fp16 output rounds these to zero
+// anyway; a bf16 output can hold them, so the bf16 stores patch that tail (act_tail4).
 // Every step is an explicit mul / fma so the scalar and the packed form
 // below round identically (the tile and tail paths must agree bit for bit).
 namespace gelu_nr {
@@ -116,6 +124,58 @@ MICLIP_DEV f32x2 quick_gelu2(f32x2 v) {
   return v * (f32x2){__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
 }
 
+// The tail a bf16 output can still hold (see gelu_nr above): where the small factor
+// 2^x of the activation is below 2^-126, y = (w h) h with h = 2^(x/2), w = v (QuickGELU,
+// x = -t; the 1 + of the denominator is below half an ulp there) or v t (GELU). Both
+// factors and every normal product stay normal; a result below 2^-126 may still flush.
+// Elsewhere y is returned untouched, so no other output bit changes. The scalar and
+// the packed epilogues call the same function: tile and tail paths agree bit for bit.
+template <int ACT>
+MICLIP_DEV float act_tail(float v, float y) {
+  if (ACT == ACT_QUICKGELU) {
+    const float t = v * kQuickGeluK;
+    if (t > 126.0f) {
+      const float h = __builtin_amdgcn_exp2f(t * -0.5f);
+      y = (v * h) * h;
+    }
+  } else if (ACT == ACT_GELU) {
+    using namespace gelu_nr;
+    const float t = __builtin_amdgcn_rcpf(__builtin_fmaf(__builtin_fabsf(v), kT, 1.0f));
+    float p = kC[0];
+#pragma unroll
+    for (int i = 1; i < 10; ++i) p = __builtin_fmaf(t, p, kC[i]);
+    const float x = __builtin_fmaf(v * v, kQ, p);
+    if (x < -126.0f) {
+      const float h = __builtin_amdgcn_exp2f(x * 0.5f);
+      y = ((v * t) * h) * h;
+    }
+  }
+  return y;
+}
+// first pre-activation at which a tail can start (t = 126 at v = -51.31; x = -126 at
+// v = -13.08): above it the stores skip act_tail
+template <int ACT>
+constexpr float act_tail_from() { return ACT == ACT_GELU ? -13.0f : -51.0f; }
+template <typename T, int ACT>
+MICLIP_DEV float act_tail1(float v, float y) {
+  if constexpr (std::is_same_v<T, __bf16> && (ACT == ACT_GELU || ACT == ACT_QUICKGELU)) {
+    if (v < act_tail_from<ACT>()) y = act_tail<ACT>(v, y);
+  }
+  return y;
+}
+template <typename T, int ACT>
+MICLIP_DEV void act_tail4(f32x2 v0, f32x2 v1, f32x2& lo, f32x2& hi) {
+  if constexpr (std::is_same_v<T, __bf16> && (ACT == ACT_GELU || ACT == ACT_QUICKGELU)) {
+    const float m = __builtin_fminf(__builtin_fminf(v0[0], v0[1]), __builtin_fminf(v1[0], v1[1]));
+    if (m < act_tail_from<ACT>()) {
+      lo[0] = act_tail1<T, ACT>(v0[0], lo[0]);
+      lo[1] = act_tail1<T, ACT>(v0[1], lo[1]);
+      hi[0] = act_tail1<T, ACT>(v1[0], hi[0]);
+      hi[1] = act_tail1<T, ACT>(v1[1], hi[1]);
+    }
+  }
+}
+
 template <int ACT>
 MICLIP_DEV float act_fn(float v) {
   // x * sigmoid(1.702 x) (clip/model.py:160-162): one mul into v_exp (base 2,
@@ -166,8 +226,9 @@ struct EpiStore {
     if constexpr (ACT == ACT_GELU || ACT == ACT_QUICKGELU) {  // packed-fp32 forms, same rounding
       const f32x2 y0 = (f32x2){v.x, v.y} + (f32x2){b.x, b.y};
       const f32x2 y1 = (f32x2){v.z, v.w} + (f32x2){b.z, b.w};
-      const f32x2 lo = ACT == ACT_GELU ? gelu_erf2(y0) : quick_gelu2(y0);
-      const f32x2 hi = ACT == ACT_GELU ? gelu_erf2(y1) : quick_gelu2(y1);
+      f32x2 lo = ACT == ACT_GELU ? gelu_erf2(y0) : quick_gelu2(y0);
+      f32x2 hi = ACT == ACT_GELU ? gelu_erf2(y1) : quick_gelu2(y1);
+      act_tail4<T, ACT>(y0, y1, lo, hi);
       o[0] = to_bits<T>(fin(lo[0]));
       o[1] = to_bits<T>(fin(lo[1]));
       o[2] = to_bits<T>(fin(hi[0]));
@@ -185,7 +246,8 @@ struct EpiStore {
     return o;
   }
   MICLIP_DEV void put1(int r, int c, float v, float b) const {
-    C[(size_t)r * ldc + c] = to_t<T>(fin(act_fn<ACT>(v + b)));
+    const float x = v + b;
+    C[(size_t)r * ldc + c] = to_t<T>(fin(act_tail1<T, ACT>(x, act_fn<ACT>(x))));
   }
 };
 
@@ -240,8 +302,9 @@ struct EpiStoreLN {
     const f32x2 y1 = z2((f32x2){v.z, v.w}, (f32x2){s.z, s.w}, st, (f32x2){b.z, b.w});
     i16x4 o;
     if constexpr (ACT == ACT_GELU || ACT == ACT_QUICKGELU) {
-      const f32x2 lo = ACT == ACT_GELU ? gelu_erf2(y0) : quick_gelu2(y0);
-      const f32x2 hi = ACT == ACT_GELU ? gelu_erf2(y1) : quick_gelu2(y1);
+      f32x2 lo = ACT == ACT_GELU ? gelu_erf2(y0) : quick_gelu2(y0);
+      f32x2 hi = ACT == ACT_GELU ? gelu_erf2(y1) : quick_gelu2(y1);
+      act_tail4<T, ACT>(y0, y1, lo, hi);
       o[0] = to_bits<T>(fin(lo[0]));
       o[1] = to_bits<T>(fin(lo[1]));
       o[2] = to_bits<T>(fin(hi[0]));
@@ -259,7 +322,8 @@ struct EpiStoreLN {
     put4ln<ASM>(r, c, v, b, *(const float4*)(colsum + c), stats[r]);
   }
   MICLIP_DEV void put1(int r, int c, float v, float b) const {
-    C[(size_t)r * ldc + c] = to_t<T>(fin(act_fn<ACT>(z(v, colsum[c], stats[r], b))));
+    const float x = z(v, colsum[c], stats[r], b);
+    C[(size_t)r * ldc + c] = to_t<T>(fin(act_tail1<T, ACT>(x, act_fn<ACT>(x))));
   }
 };
 template <class Epi> struct IsLN : std::false_type {};

@@ -2004,16 +2004,18 @@ hipError_t gemm_null(int dtype, const void* A, const void* W, float* C, int M, i
 }
 
 hipError_t gemm_patch(int dtype, const void* A, const void* W, const float* pos, void* X, int M,
-                      int N, int K, int np, hipStream_t s, int resid16) {
+                      int N, int K, int np, hipStream_t s, int resid16, int variant) {
   if (np <= 0 || M % np) return hipErrorInvalidValue;
   if (resid16) {   // patch embedding into the fp16 stream (fp16 or bf16 operands)
     if (dtype == kBF16)
-      return launch<__bf16>(A, W, M, N, K, EpiPatch<_Float16>{(_Float16*)X, pos, N, np}, s);
-    return launch<_Float16>(A, W, M, N, K, EpiPatch<_Float16>{(_Float16*)X, pos, N, np}, s);
+      return launch<__bf16>(A, W, M, N, K, EpiPatch<_Float16>{(_Float16*)X, pos, N, np}, s,
+                            variant);
+    return launch<_Float16>(A, W, M, N, K, EpiPatch<_Float16>{(_Float16*)X, pos, N, np}, s,
+                            variant);
   }
   if (dtype == kF16)
-    return launch<_Float16>(A, W, M, N, K, EpiPatch<float>{(float*)X, pos, N, np}, s);
-  return launch<__bf16>(A, W, M, N, K, EpiPatch<float>{(float*)X, pos, N, np}, s);
+    return launch<_Float16>(A, W, M, N, K, EpiPatch<float>{(float*)X, pos, N, np}, s, variant);
+  return launch<__bf16>(A, W, M, N, K, EpiPatch<float>{(float*)X, pos, N, np}, s, variant);
 }
 
 }  // namespace miclip

@@ -43,9 +43,10 @@ hipError_t gemm_null(int dtype, const void* A, const void* W, float* C, int M, i
                      hipStream_t s, int variant = 0);
 // Patch-embed epilogue: row m = b*np + p of the patch GEMM goes to token row
 // b*(np+1) + 1 + p of X (fp32, or fp16 when resid16; ld = N), plus positional
-// embedding row 1 + p.
+// embedding row 1 + p. `variant` as gemm_store (the model passes 0; op tests force a tile).
 hipError_t gemm_patch(int dtype, const void* A, const void* W, const float* pos, void* X,
-                      int M, int N, int K, int np, hipStream_t s, int resid16 = 0);
+                      int M, int N, int K, int np, hipStream_t s, int resid16 = 0,
+                      int variant = 0);
 
 // ---- MX-fp8 (OCP e4m3 + E8M0 per 32 k) operands and GEMM (gemm_mx.hip) ----
 // Scale plane bytes of a [rows, K] operand (tiled, see mx_scale_index).

@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MICLIP_LIB", os.path.join(_HERE, "libmiclip.so"))
 
-ABI_VERSION = 9          # include/miclip.h MICLIP_ABI_VERSION
+ABI_VERSION = 10         # include/miclip.h MICLIP_ABI_VERSION
 MICLIP_FP16 = 0
 MICLIP_BF16 = 1
 MICLIP_MXFP8 = 2
@@ -43,6 +43,7 @@ EXPORTS = (
     "miclip_model_destroy", "miclip_last_error", "miclip_abi_version",
     "miclip_model_bytes", "miclip_model_flags", "miclip_model_set_option", "miclip_set_gemm_variant", "miclip_set_profiling", "miclip_profile_read", "miclip_set_splits", "miclip_image_splits",
     "miclip_op_gemm", "miclip_op_gemm_splitk", "miclip_op_ln_stats", "miclip_op_ln_fold", "miclip_op_gemm_ln",
+    "miclip_op_gemm_patch", "miclip_op_class_token", "miclip_op_layernorm_rows",
     "miclip_op_layernorm", "miclip_op_attention", "miclip_op_attention_q0", "miclip_op_im2col", "miclip_preprocess", "miclip_preprocess_aug",
     "miclip_row_norms", "miclip_class_centroids", "miclip_proto_scores",
     "miclip_kmeans_scratch_bytes", "miclip_kmeans_seed", "miclip_kmeans_lloyd",
@@ -142,6 +143,11 @@ def load_library(path: str = None):
         "miclip_profile_read": ([vp, ctypes.POINTER(MiclipKernelStat), i32, i32], ctypes.c_int),
         "miclip_op_gemm": ([i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp], ctypes.c_int),
         "miclip_op_layernorm": ([i32, vp, vp, vp, vp, i32, i32, i32, vp], ctypes.c_int),
+        "miclip_op_layernorm_rows": ([i32, vp, vp, i32, vp, vp, vp, i32, i32, i32, vp],
+                                     ctypes.c_int),
+        "miclip_op_gemm_patch": ([i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
+                                 ctypes.c_int),
+        "miclip_op_class_token": ([vp, vp, vp, i32, i32, i32, i32, vp], ctypes.c_int),
         "miclip_op_attention_q0": ([i32, vp, vp, i32, i32, i32, i32, vp], ctypes.c_int),
         "miclip_op_im2col": ([i32, i32, vp, vp, i32, i32, i32, i32, i32, vp], ctypes.c_int),
         "miclip_op_ln_stats": ([vp, vp, i32, i32, vp, vp], ctypes.c_int),

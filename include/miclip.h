@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define MICLIP_ABI_VERSION 9
+#define MICLIP_ABI_VERSION 10
 
 enum miclip_status {
   MICLIP_OK = 0,
@@ -719,6 +719,29 @@ int miclip_op_gemm_ln(int32_t dtype, const void* A, const void* Wf, const float*
  * dtype); bit 1: in fp16 (the fp16 residual stream; dtype MICLIP_FP16 only), else fp32. */
 int miclip_op_layernorm(int32_t dtype, const void* in, const float* gamma, const float* beta,
                         void* out, int32_t flags, int32_t R, int32_t D, void* stream);
+/* miclip_op_layernorm over gathered rows: output row r normalises input row rows[r]
+ * (device int32 [R]; repeats and any order allowed), or row r * in_stride_rows when rows
+ * is NULL (in_stride_rows >= 1): ln_post on the CLS rows (stride ntok), ln_final on the
+ * EOT rows (clip/model.py:226-229, :349-354). flags bits 0 and 1 as above; bit 2:
+ * L2-normalise each output row after the affine (F.normalize, eps 1e-12: the feature
+ * cache's fused normalisation). D % 256 == 0, D <= 1536. */
+int miclip_op_layernorm_rows(int32_t dtype, const void* in, const int32_t* rows,
+                             int32_t in_stride_rows, const float* gamma, const float* beta,
+                             void* out, int32_t flags, int32_t R, int32_t D, void* stream);
+
+/* The patch embedding's GEMM (EpiPatch): row m = b * np + p of A[M,K] . W[N,K]^T goes to
+ * token row b * (np + 1) + 1 + p of X [B * (np + 1), N] plus positional row pos[1 + p]
+ * (pos fp32 [np + 1, N]); X fp32, or fp16 when resid16 (one RNE of the fp32 sum). M % np
+ * == 0; shapes as miclip_op_gemm. variant 0 = by size (the model's call), 128 / 256..258,
+ * 260 = force the 128x128 / one-tile 256x256 kernels. Replaces conv1 + the positional add
+ * (clip/model.py:216-222). Row b * (np + 1) of X is left to miclip_op_class_token. */
+int miclip_op_gemm_patch(int32_t dtype, const void* A, const void* W, const float* pos, void* X,
+                         int32_t M, int32_t N, int32_t K, int32_t np, int32_t resid16,
+                         int32_t variant, void* stream);
+/* X[b * ntok, :] = cls + pos[0, :] for b < B (cls, pos fp32 [D]; X fp32, or fp16 when
+ * resid16): the class-embedding row (clip/model.py:220-221). */
+int miclip_op_class_token(const float* cls, const float* pos, void* X, int32_t B, int32_t ntok,
+                          int32_t D, int32_t resid16, void* stream);
 
 /* softmax(Q K^T / sqrt(dh) + mask) V per head over a packed qkv [B*N, 3*H*dh]
  * buffer, out [B*N, H*dh]; replaces F.scaled_dot_product_attention inside

@@ -43,7 +43,7 @@ def test_symbols_are_exported_and_abi_stays_9(lib):
     from miclip import _lib
     for s in ("miclip_ft_rows_scratch_bytes", "miclip_ft_grad_rows"):
         assert s in _lib.EXPORTS and hasattr(lib, s)
-    assert lib.miclip_abi_version() == 9 == _lib.ABI_VERSION
+    assert lib.miclip_abi_version() == 10 == _lib.ABI_VERSION
 
 
 def test_rows_scratch_is_the_plain_scratch_plus_the_index_area(lib):

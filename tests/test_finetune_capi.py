@@ -59,7 +59,7 @@ def test_new_symbols_are_exported_and_abi_stays_9(lib):
     for s in NEW:
         assert s in _lib.EXPORTS
         assert hasattr(lib, s)
-    assert lib.miclip_abi_version() == 9 == _lib.ABI_VERSION
+    assert lib.miclip_abi_version() == 10 == _lib.ABI_VERSION
 
 
 def test_gemm_tn_plan_is_a_function_of_the_shape(lib):

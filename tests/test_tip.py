@@ -159,11 +159,11 @@ def test_exports_and_symbols():
     names = ("miclip_tip_scratch_bytes", "miclip_tip_keys", "miclip_tip_affinity",
              "miclip_tip_grid", "miclip_tip_logits")
     assert set(names) <= set(_lib.EXPORTS)
-    assert _lib.ABI_VERSION == 9
+    assert _lib.ABI_VERSION == 10
     lib = _lib.load_library()
     for name in names:
         assert getattr(lib, name).argtypes is not None
-    assert lib.miclip_abi_version() == 9
+    assert lib.miclip_abi_version() == 10
     # the scratch query is host-only: positive inside the limits, 0 outside
     assert lib.miclip_tip_scratch_bytes(1, 1, 16, 1, 1, 1) > 0
     assert lib.miclip_tip_scratch_bytes(1 << 24, 65536, 1024, 1024, 1024, 64) > 0

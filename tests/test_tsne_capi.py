@@ -44,7 +44,7 @@ def test_new_symbols_are_exported_and_abi_stays_9(lib):
     for s in NEW:
         assert s in _lib.EXPORTS
         assert hasattr(lib, s)
-    assert lib.miclip_abi_version() == 9
+    assert lib.miclip_abi_version() == 10
 
 
 def test_scratch_bytes(lib):
