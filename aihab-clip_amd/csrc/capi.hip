@@ -1297,6 +1297,86 @@ int miclip_tip_logits(const float* affinity, const int32_t* key_labels, const fl
   return 0;
 }
 
+// ---- Tip-Adapter-F: training the cache keys (tip_train.hip) ----
+static bool tipf_args_ok(int64_t n, int64_t b, int64_t Nk, int64_t E, int64_t C, int64_t G,
+                         std::string& why) {
+  const char* bad = tipf_bad_arg(n, b, Nk, E, C, G);
+  if (!bad) return true;
+  why = std::string(bad) + ", got n=" + std::to_string(n) + " b=" + std::to_string(b) +
+        " Nk=" + std::to_string(Nk) + " E=" + std::to_string(E) + " C=" + std::to_string(C) +
+        " G=" + std::to_string(G);
+  return false;
+}
+
+int64_t miclip_tipf_scratch_bytes(int32_t b, int32_t Nk, int32_t E, int32_t C, int32_t G) {
+  return (int64_t)tipf_scratch_bytes(b, Nk, E, C, G);
+}
+
+int miclip_tipf_prepare(const int32_t* key_labels, int32_t Nk, int32_t C, void* scratch,
+                        void* stream) {
+  if (!key_labels) return fail(MICLIP_EINVAL, "null argument: key_labels");
+  if (!scratch) return fail(MICLIP_EINVAL, "null argument: scratch");
+  std::string why;
+  if (!tip_args_ok(kTipNk | kTipC, 0, Nk, 0, C, 0, 0, why)) return fail(MICLIP_EINVAL, why);
+  if ((uintptr_t)scratch & 255) return fail(MICLIP_EINVAL, "scratch: expected a 256-byte aligned pointer");
+  MICLIP_HIP(tipf_prepare(key_labels, Nk, C, scratch, (hipStream_t)stream));
+  return 0;
+}
+
+int miclip_tipf_step(const void* F, int32_t f_dtype, int32_t n, const int64_t* rows_host,
+                     int32_t b, const int32_t* labels, const float* clip_logits,
+                     const int32_t* key_labels, float* keys, float* m, float* v, const float* lr,
+                     const float* betas, const float* alphas, int32_t Nk, int32_t E, int32_t C,
+                     int32_t G, float lr_factor, float weight_decay, float eps, int32_t step,
+                     float* history, float* grad_out, void* scratch, void* stream) {
+  const std::pair<const void*, const char*> ptrs[] = {
+      {F, "F"}, {rows_host, "rows_host"}, {labels, "labels"}, {clip_logits, "clip_logits"},
+      {key_labels, "key_labels"}, {keys, "keys"}, {m, "m"}, {v, "v"}, {lr, "lr"},
+      {betas, "betas"}, {alphas, "alphas"}, {history, "history"}, {scratch, "scratch"}};
+  for (const auto& a : ptrs)
+    if (!a.first) return fail(MICLIP_EINVAL, std::string("null argument: ") + a.second);
+  std::string why;
+  if (!tip_dtype_arg_ok(f_dtype, "f_dtype", why)) return fail(MICLIP_EINVAL, why);
+  if (!tipf_args_ok(n, b, Nk, E, C, G, why)) return fail(MICLIP_EINVAL, why);
+  if (step < 1) return fail(MICLIP_EINVAL, "step must be >= 1, got " + std::to_string(step));
+  if (!std::isfinite(lr_factor))
+    return fail(MICLIP_EINVAL, "lr_factor must be finite, got " + std::to_string(lr_factor));
+  if (!(weight_decay >= 0.f) || !std::isfinite(weight_decay))
+    return fail(MICLIP_EINVAL, "weight_decay must be finite and >= 0, got " + std::to_string(weight_decay));
+  if (!(eps >= 0.f) || !std::isfinite(eps))
+    return fail(MICLIP_EINVAL, "eps must be finite and >= 0, got " + std::to_string(eps));
+  if (((uintptr_t)F & 15) || ((uintptr_t)keys & 15) || ((uintptr_t)m & 15) || ((uintptr_t)v & 15))
+    return fail(MICLIP_EINVAL, "F / keys / m / v: expected 16-byte aligned operands");
+  if ((uintptr_t)scratch & 255) return fail(MICLIP_EINVAL, "scratch: expected a 256-byte aligned pointer");
+  for (int32_t r = 0; r < b; ++r)
+    if (rows_host[r] < 0 || rows_host[r] >= n)
+      return fail(MICLIP_EINVAL, "rows_host[" + std::to_string(r) + "] must be in [0, n), got " +
+                                     std::to_string(rows_host[r]) + " with n=" + std::to_string(n));
+  MICLIP_HIP(tipf_step(f_dtype, F, n, rows_host, b, labels, clip_logits, key_labels, keys, m, v,
+                       lr, betas, alphas, Nk, E, C, G, lr_factor, weight_decay, eps, step, history,
+                       grad_out, scratch, (hipStream_t)stream));
+  return 0;
+}
+
+int miclip_tipf_keep_best(const int32_t* counts, int32_t epoch, const float* keys,
+                          float* best_keys, int32_t* best_count, int32_t* best_epoch, int32_t Nk,
+                          int32_t E, int32_t G, void* stream) {
+  const std::pair<const void*, const char*> ptrs[] = {
+      {counts, "counts"}, {keys, "keys"}, {best_keys, "best_keys"}, {best_count, "best_count"},
+      {best_epoch, "best_epoch"}};
+  for (const auto& a : ptrs)
+    if (!a.first) return fail(MICLIP_EINVAL, std::string("null argument: ") + a.second);
+  std::string why;
+  if (!tip_args_ok(kTipNk | kTipE, 0, Nk, E, 0, 0, 0, why)) return fail(MICLIP_EINVAL, why);
+  if (G < 1 || G > 64) return fail(MICLIP_EINVAL, "G must be in 1..64, got " + std::to_string(G));
+  if (epoch < 0) return fail(MICLIP_EINVAL, "epoch must be >= 0, got " + std::to_string(epoch));
+  if (((uintptr_t)keys & 15) || ((uintptr_t)best_keys & 15))
+    return fail(MICLIP_EINVAL, "keys / best_keys: expected 16-byte aligned operands");
+  MICLIP_HIP(tipf_keep_best(counts, epoch, keys, best_keys, best_count, best_epoch, Nk, E, G,
+                            (hipStream_t)stream));
+  return 0;
+}
+
 // ---- last-block fine-tuning (finetune.hip) ----
 static bool gemm_tn_args_ok(int32_t M, int32_t Nn, int32_t K, std::string& why) {
   if (M < 1 || M > 0x7fffffff - 64) why = "M: expected M >= 1";

@@ -262,6 +262,36 @@ hipError_t tip_grid(const float* aff, const int32_t* key_labels, const float* Z,
 hipError_t tip_logits(const float* aff, const int32_t* key_labels, const float* Z, float beta,
                       float alpha, float* out, int Nq, int Nk, int C, void* scratch,
                       hipStream_t s);
+// tip_grid's stable counting sort alone: order [Nk] at scratch, offsets [C + 1] at
+// scratch + tip_sort_offsets_at(Nk) (the head of tip_scratch_bytes' layout).
+size_t tip_sort_offsets_at(int Nk);
+hipError_t tip_sort_keys(const int32_t* key_labels, int Nk, int C, void* scratch, hipStream_t s);
+
+// ---- Tip-Adapter-F: training the cache keys (tip_train.hip), fp32 ----
+// n cached rows, b batch rows, Nk keys, E width, C classes, G configurations: 1 <= n <=
+// 2^24, 1 <= b <= 4096, 1 <= G <= 64, Nk / E / C as tip_bad_arg; tipf_bad_arg names the
+// first violated limit or returns null. scratch: tipf_scratch_bytes (0 outside the
+// limits), 256-B aligned; tipf_prepare sorts the key labels into its head once per fit.
+const char* tipf_bad_arg(int64_t n, int64_t b, int64_t Nk, int64_t E, int64_t C, int64_t G);
+size_t tipf_scratch_bytes(int b, int Nk, int E, int C, int G);
+hipError_t tipf_prepare(const int32_t* key_labels, int Nk, int C, void* scratch, hipStream_t s);
+// One AdamW step of K / m / v [G, Nk, E] on the b rows rows_host (HOST int64, each in
+// [0, n), checked before any launch) of F [n, E] (f_dtype kIn32 / kF16 / kBF16), Z [n, C]
+// = 100 F W and labels [n] int32: loss = mean CE(Z_b + alpha_g S(beta_g)), step >= 1,
+// lr_t = lrs[g] * lr_factor. history [G, 2] = {mean CE, correct rows} before the update;
+// grad_out [G, Nk, E] or null.
+hipError_t tipf_step(int f_dtype, const void* F, int n, const int64_t* rows_host, int b,
+                     const int32_t* labels, const float* Z, const int32_t* key_labels, float* K,
+                     float* m, float* v, const float* lrs, const float* betas,
+                     const float* alphas, int Nk, int E, int C, int G, float lr_factor,
+                     float weight_decay, float eps, int step, float* history, float* grad_out,
+                     void* scratch, hipStream_t s);
+// counts [>= epoch + 1, G] int32: where counts[epoch, g] is strictly greater than every
+// earlier epoch's count and than 0, best_keys[g] = keys[g], best_count[g] = the count,
+// best_epoch[g] = epoch.
+hipError_t tipf_keep_best(const int32_t* counts, int epoch, const float* keys, float* best_keys,
+                          int32_t* best_count, int32_t* best_epoch, int Nk, int E, int G,
+                          hipStream_t s);
 
 // ---- last-block fine-tuning of the image tower (finetune.hip) ----
 // gemm_tn: G [Nn, K] fp32 = sum_m A[m, Nn] * X[m, K] (A, X compute dtype, row-major,

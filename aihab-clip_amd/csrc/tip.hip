@@ -347,6 +347,13 @@ const char* tip_bad_arg(unsigned which, int64_t Nq, int64_t Nk, int64_t E, int64
   return nullptr;
 }
 
+size_t tip_sort_offsets_at(int Nk) { return tip_order_bytes(Nk); }
+
+hipError_t tip_sort_keys(const int32_t* key_labels, int Nk, int C, void* scratch, hipStream_t s) {
+  if (tip_bad_arg(kTipNk | kTipC, 0, Nk, 0, C, 0, 0)) return hipErrorInvalidValue;
+  return tip_sort(key_labels, Nk, C, scratch, s);
+}
+
 size_t tip_scratch_bytes(int Nq, int Nk, int E, int C, int nb, int na) {
   if (tip_bad_arg(kTipAll, Nq, Nk, E, C, nb, na)) return 0;
   return tip_order_bytes(Nk) + (((size_t)(C + 1) * 4 + 255) & ~(size_t)255);

@@ -23,8 +23,9 @@ from .evaluation import (ClassificationTracker, Evaluator, L2MetricsAccumulator,
                          run_validation)
 from .model import CLIP, build_model
 from .preprocess import Transform
-from .tip import (beta_alpha_lists, build_cache_model, cache_model_from_views, search_hp_tip,
-                  tip_accuracy_grid, tip_logits)
+from .tip import (AdapterFit, beta_alpha_lists, build_cache_model, cache_model_from_views,
+                  fit_adapter, fit_adapter_grid, search_hp_tip, tip_accuracy_grid, tip_adapter_f,
+                  tip_logits)
 from .weights import generate_state_dict, synthetic_images
 
 __all__ = ["available_models", "load", "tokenize", "build_model", "CLIP", "CLIPConfig",
@@ -33,7 +34,8 @@ __all__ = ["available_models", "load", "tokenize", "build_model", "CLIP", "CLIPC
            "aggregate_logits_to_l2", "map_l3_targets_to_l2", "augment",
            "build_clip_transforms", "embed_vis", "tsne", "pca_reduce", "visualize_cache",
            "TsneResult", "tip", "build_cache_model", "cache_model_from_views", "search_hp_tip",
-           "tip_accuracy_grid", "tip_logits", "beta_alpha_lists"]
+           "tip_accuracy_grid", "tip_logits", "beta_alpha_lists", "AdapterFit",
+           "fit_adapter_grid", "fit_adapter", "tip_adapter_f"]
 
 
 class SeededWeightsWarning(UserWarning):

@@ -51,6 +51,8 @@ EXPORTS = (
     "miclip_prolip_grad", "miclip_prolip_adam",
     "miclip_tip_scratch_bytes", "miclip_tip_keys", "miclip_tip_affinity", "miclip_tip_grid",
     "miclip_tip_logits",
+    "miclip_tipf_scratch_bytes", "miclip_tipf_prepare", "miclip_tipf_step",
+    "miclip_tipf_keep_best",
     "miclip_gemm_tn_ws_bytes", "miclip_gemm_tn_plan", "miclip_op_gemm_tn", "miclip_ft_adam",
     "miclip_ft_proj_scratch_bytes", "miclip_ft_proj_grad",
     "miclip_encode_image_trunk", "miclip_ft_layout", "miclip_ft_scratch_bytes", "miclip_ft_grad",
@@ -191,6 +193,11 @@ def load_library(path: str = None):
         "miclip_tip_grid": ([vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp],
                             ctypes.c_int),
         "miclip_tip_logits": ([vp, vp, vp, i32, i32, i32, f32, f32, vp, vp, vp], ctypes.c_int),
+        "miclip_tipf_scratch_bytes": ([i32, i32, i32, i32, i32], i64),
+        "miclip_tipf_prepare": ([vp, i32, i32, vp, vp], ctypes.c_int),
+        "miclip_tipf_step": ([vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32,
+                              i32, i32, f32, f32, f32, i32, vp, vp, vp, vp], ctypes.c_int),
+        "miclip_tipf_keep_best": ([vp, i32, vp, vp, vp, vp, i32, i32, i32, vp], ctypes.c_int),
         "miclip_gemm_tn_ws_bytes": ([i32, i32, i32], i64),
         "miclip_gemm_tn_plan": ([i32, i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)],
                                 ctypes.c_int),

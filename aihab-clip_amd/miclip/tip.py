@@ -33,10 +33,20 @@ Deliberate departures from the reference:
   * tqdm's progress bar is not reproduced; the print lines are.
 An all-zero mean row yields a non-finite key, as in the reference (:48 divides by the
 norm without a floor). There is no CPU fallback.
+
+Tip-Adapter-F, the fine-tuned variant that `adapter=` is the hook of, trains the keys on
+cached joint-space features in the kernels of csrc/tip_train.hip (fit_adapter_grid,
+fit_adapter, tip_adapter_f at the end of this file): AdamW under a cosine schedule, a
+grid of (lr, beta, alpha) configurations per launch, the best epoch kept by a device
+kernel, no host wait until the result is read. The recipe is stated in
+fit_adapter_grid's docstring and in include/miclip.h; the reference checkout does not
+contain that loop.
 """
 import ctypes
+import dataclasses
+import math
 from pathlib import Path
-from typing import List, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -48,7 +58,8 @@ _DTYPES = {torch.float32: _lib.MICLIP_F32, torch.float16: _lib.MICLIP_FP16,
            torch.bfloat16: _lib.MICLIP_BF16}
 
 __all__ = ["build_cache_model", "cache_model_from_views", "search_hp_tip", "tip_accuracy_grid",
-           "tip_logits", "beta_alpha_lists", "scan_count_grid", "cls_acc"]
+           "tip_logits", "beta_alpha_lists", "scan_count_grid", "cls_acc", "AdapterFit",
+           "fit_adapter_grid", "fit_adapter", "tip_adapter_f", "cosine_lr_factor"]
 
 
 def _ptr(t):
@@ -326,3 +337,275 @@ def build_cache_model(cfg, clip_model, train_loader_cache, task, proj):
         cache_values = torch.load(cache_dir / f'values_task{task}.pt', map_location=dev,
                                   weights_only=True)
     return cache_keys, cache_values
+
+
+# ---- Tip-Adapter-F: the cache keys trained on cached features (csrc/tip_train.hip) ----
+
+_KEEP_EPOCHS_MAX_BYTES = 1 << 30   # keep_epochs is a test and debug aid
+
+
+@dataclasses.dataclass
+class AdapterFit:
+    """Result of fit_adapter_grid, all tensors on the device:
+    keys [G, Nk, E] after the last step; best_keys [G, Nk, E], best_epoch [G] and
+    best_count [G] (int32) of the first epoch whose evaluation count is strictly greater
+    than every earlier one, from 0 (the initial keys, -1 and 0 when none is); history
+    [steps, G, 2] = {mean CE, correct rows} of every training batch before its update;
+    eval_counts [epochs, G] int32 (None without evaluation rows); epoch_keys
+    [epochs, G, Nk, E] with keep_epochs, else None; lrs / betas / alphas as given;
+    steps_per_epoch and n for reading the history."""
+    keys: torch.Tensor
+    best_keys: torch.Tensor
+    best_epoch: torch.Tensor
+    best_count: torch.Tensor
+    history: torch.Tensor
+    eval_counts: Optional[torch.Tensor]
+    epoch_keys: Optional[torch.Tensor]
+    lrs: List[float]
+    betas: List[float]
+    alphas: List[float]
+    steps_per_epoch: int
+    n: int
+
+
+def _finite_list(name, xs):
+    try:
+        out = [float(x) for x in xs]
+    except TypeError:
+        raise TypeError(f"Expected {name} as a sequence of numbers.") from None
+    if not all(math.isfinite(x) for x in out):
+        raise ValueError(f"{name} must be finite, got {out}.")
+    return out
+
+
+def _check_views(train_views, E):
+    views = [train_views] if isinstance(train_views, torch.Tensor) else \
+        (list(train_views) if train_views is not None else [])
+    if not views:
+        raise ValueError("Empty inputs: no training views.")
+    for k, x in enumerate(views):
+        if not isinstance(x, torch.Tensor) or x.ndim != 2 or not x.is_floating_point():
+            raise ValueError(f"Expected train_views[{k}] as a floating [n, E] tensor.")
+        if x.shape[1] != E:
+            raise ValueError(f"train_views[{k}] has width {x.shape[1]}, cache_keys [E, Nk] has "
+                             f"E = {E}.")
+        if x.shape != views[0].shape or x.dtype != views[0].dtype:
+            raise ValueError(f"train_views[{k}] differs from train_views[0] in shape or dtype.")
+    return views
+
+
+def cosine_lr_factor(t: int, T: int) -> float:
+    """CosineAnnealingLR(T)'s factor at 1-based step t: 0.5 (1 + cos(pi (t - 1) / T))."""
+    return 0.5 * (1.0 + math.cos(math.pi * (t - 1) / T))
+
+
+def fit_adapter_grid(cache_keys, cache_values, clip_weights, train_views, train_labels,
+                     lrs: Sequence[float], betas: Sequence[float], alphas: Sequence[float], *,
+                     epochs: int, batch_size: int = 256, weight_decay: float = 0.01,
+                     eps: float = 1e-4, seed: int = 0, shuffle: bool = True, eval_features=None,
+                     eval_labels=None, keep_epochs: bool = False) -> AdapterFit:
+    """Tip-Adapter-F training of the cache keys for G = len(lrs) configurations
+    (lrs[g], betas[g], alphas[g]) at once, on cached joint-space features.
+
+    cache_keys [E, Nk], cache_values one-hot [Nk, <= C], clip_weights [E, C] as for
+    search_hp_tip; train_views: one [n, E] tensor or a list of V of them (fp32 / fp16 /
+    bf16), train_labels [n] in [0, C). Epoch e trains on view e % V in the order
+    finetune.cache_order(n, seed, e, shuffle), in batches of batch_size rows (the last one
+    partial and averaged over its own rows); the cosine schedule advances once per step
+    over T = epochs * steps per epoch; AdamW with betas 0.9 / 0.999.
+
+    With eval_features [Nq, E] and eval_labels [Nq], every configuration is evaluated
+    after every epoch at its own (beta, alpha) with the kernels of tip_accuracy_grid, and
+    the keys of the first epoch that beats every earlier count (from 0) are kept: a device
+    kernel takes that decision. Without them best_keys is keys and best_epoch is
+    epochs - 1. The host checks come first (cache_values and the labels are copied to the
+    host once); after them nothing waits for the device. keep_epochs keeps every epoch's
+    keys (refused above 1 GiB)."""
+    lrs, betas, alphas = (_finite_list(nm, xs) for nm, xs in
+                          (("lrs", lrs), ("betas", betas), ("alphas", alphas)))
+    G = len(lrs)
+    if G < 1 or len(betas) != G or len(alphas) != G:
+        raise ValueError(f"lrs, betas and alphas must have one common length >= 1, got "
+                         f"{len(lrs)}, {len(betas)}, {len(alphas)}.")
+    if G > 64:
+        raise ValueError(f"at most 64 configurations per fit, got {G}.")
+    for name, val, lo in (("epochs", epochs, 1), ("batch_size", batch_size, 1)):
+        if isinstance(val, bool) or not isinstance(val, int) or val < lo:
+            raise ValueError(f"{name} must be an integer >= {lo}, got {val!r}.")
+    if batch_size > 4096:
+        raise ValueError(f"batch_size must be at most 4096, got {batch_size}.")
+    weight_decay, eps = float(weight_decay), float(eps)
+    if not (math.isfinite(weight_decay) and weight_decay >= 0):
+        raise ValueError(f"weight_decay must be finite and >= 0, got {weight_decay}.")
+    if not (math.isfinite(eps) and eps >= 0):
+        raise ValueError(f"eps must be finite and >= 0, got {eps}.")
+    if not isinstance(cache_keys, torch.Tensor) or cache_keys.ndim != 2:
+        raise ValueError("Expected cache_keys as a floating [rows, cols] tensor.")
+    views = _check_views(train_views, int(cache_keys.shape[0]))
+    n, Nk, E, C, key_lab = _check_inputs(cache_keys, cache_values, views[0], clip_weights)
+    lab = _check_labels("train_labels", train_labels, n, C)
+    if (eval_features is None) != (eval_labels is None):
+        raise ValueError("eval_features and eval_labels go together.")
+    evaluate = eval_features is not None
+    if evaluate:
+        Nq = _check_inputs(cache_keys, cache_values, eval_features, clip_weights)[0]
+        elab = _check_labels("eval_labels", eval_labels, Nq, C)
+    if keep_epochs and epochs * G * Nk * E * 4 > _KEEP_EPOCHS_MAX_BYTES:
+        raise ValueError(f"keep_epochs would hold {epochs * G * Nk * E * 4} bytes, more than "
+                         f"{_KEEP_EPOCHS_MAX_BYTES}.")
+    from .finetune import cache_order, cache_view
+
+    bmax = min(batch_size, n)
+    steps_per_epoch = (n + batch_size - 1) // batch_size
+    T = epochs * steps_per_epoch
+    dev = _device_of(*views, cache_keys, clip_weights)
+    lib = _lib.load_library()
+    nbytes = lib.miclip_tipf_scratch_bytes(bmax, Nk, E, C, G)
+    if nbytes <= 0:
+        raise ValueError(f"unsupported shapes b={bmax}, Nk={Nk}, E={E}, C={C}, G={G}.")
+    fs = [_feature_operand(x, dev) for x in views]
+    with torch.cuda.device(dev):
+        stream = _lib.stream_handle(dev)
+        f32 = dict(device=dev, dtype=torch.float32)
+        wt = clip_weights.detach().to(dev, torch.float32).t().contiguous()          # [C, E]
+
+        def clip_logits(f):
+            z = torch.empty(f.shape[0], C, **f32)
+            _lib.check(lib.miclip_tip_affinity(_ptr(f), _DTYPES[f.dtype], _ptr(wt), f.shape[0], C,
+                                               E, 100.0, _ptr(z), stream), "miclip_tip_affinity")
+            return z
+
+        zs = [clip_logits(f) for f in fs]            # independent of the keys: once per view
+        k0 = cache_keys.detach().to(dev, torch.float32).t().contiguous()            # [Nk, E]
+        keys = k0.unsqueeze(0).repeat(G, 1, 1).contiguous()
+        m, v = torch.zeros_like(keys), torch.zeros_like(keys)
+        lr_d, beta_d, alpha_d = (torch.tensor(x, dtype=torch.float32).to(dev)
+                                 for x in (lrs, betas, alphas))
+        lab_d, key_lab_d = lab.to(dev), key_lab.to(dev)
+        history = torch.zeros(T, G, 2, **f32)
+        scratch = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+        _lib.check(lib.miclip_tipf_prepare(_ptr(key_lab_d), Nk, C, _ptr(scratch), stream),
+                   "miclip_tipf_prepare")
+        best_keys = eval_counts = epoch_keys = None
+        if evaluate:
+            ef = _feature_operand(eval_features, dev)
+            ez, elab_d = clip_logits(ef), elab.to(dev)
+            aff = torch.empty(Nq, Nk, **f32)
+            tip_scratch = torch.empty(lib.miclip_tip_scratch_bytes(Nq, Nk, E, C, 1, 1), device=dev,
+                                      dtype=torch.uint8)
+            eval_counts = torch.zeros(epochs, G, device=dev, dtype=torch.int32)
+            best_keys = keys.clone()
+            best_count = torch.zeros(G, device=dev, dtype=torch.int32)
+            best_epoch = torch.full((G,), -1, device=dev, dtype=torch.int32)
+        if keep_epochs:
+            epoch_keys = torch.empty(epochs, G, Nk, E, **f32)
+
+        t = 0
+        for e in range(epochs):
+            vi = cache_view(e, len(fs))
+            order = cache_order(n, seed, e, shuffle)
+            for s in range(steps_per_epoch):
+                rows = order[s * batch_size:(s + 1) * batch_size].contiguous()
+                t += 1
+                _lib.check(lib.miclip_tipf_step(
+                    _ptr(fs[vi]), _DTYPES[fs[vi].dtype], n, ctypes.c_void_p(rows.data_ptr()),
+                    int(rows.shape[0]), _ptr(lab_d), _ptr(zs[vi]), _ptr(key_lab_d), _ptr(keys),
+                    _ptr(m), _ptr(v), _ptr(lr_d), _ptr(beta_d), _ptr(alpha_d), Nk, E, C, G,
+                    cosine_lr_factor(t, T), weight_decay, eps, t, _ptr(history[t - 1]), None,
+                    _ptr(scratch), stream), "miclip_tipf_step")
+            if evaluate:
+                for g in range(G):
+                    _lib.check(lib.miclip_tip_affinity(_ptr(ef), _DTYPES[ef.dtype], _ptr(keys[g]),
+                                                       Nq, Nk, E, 1.0, _ptr(aff), stream),
+                               "miclip_tip_affinity")
+                    _lib.check(lib.miclip_tip_grid(
+                        _ptr(aff), _ptr(key_lab_d), _ptr(ez), _ptr(elab_d), _ptr(beta_d[g:]),
+                        _ptr(alpha_d[g:]), Nq, Nk, C, 1, 1, _ptr(eval_counts[e, g:]),
+                        _ptr(tip_scratch), stream), "miclip_tip_grid")
+                _lib.check(lib.miclip_tipf_keep_best(_ptr(eval_counts), e, _ptr(keys),
+                                                     _ptr(best_keys), _ptr(best_count),
+                                                     _ptr(best_epoch), Nk, E, G, stream),
+                           "miclip_tipf_keep_best")
+            if keep_epochs:
+                epoch_keys[e].copy_(keys)
+        if not evaluate:
+            best_keys = keys
+            best_count = torch.zeros(G, device=dev, dtype=torch.int32)
+            best_epoch = torch.full((G,), epochs - 1, device=dev, dtype=torch.int32)
+    return AdapterFit(keys=keys, best_keys=best_keys, best_epoch=best_epoch, best_count=best_count,
+                      history=history, eval_counts=eval_counts, epoch_keys=epoch_keys, lrs=lrs,
+                      betas=betas, alphas=alphas, steps_per_epoch=steps_per_epoch, n=n)
+
+
+def _linear_from_keys(best_keys, fit):
+    Nk, E = (int(s) for s in best_keys.shape)
+    adapter = torch.nn.Linear(E, Nk, bias=False).to(best_keys.device, torch.float32)
+    with torch.no_grad():
+        adapter.weight.copy_(best_keys)
+    adapter.fit = fit
+    return adapter
+
+
+def fit_adapter(cache_keys, cache_values, clip_weights, train_views, train_labels, lr: float,
+                beta: float, alpha: float, **kwargs):
+    """fit_adapter_grid for one configuration, as the recipe's adapter: an
+    nn.Linear(E, Nk, bias=False) on the device whose weight is the best keys, with the
+    AdapterFit attached as `.fit`. It can be passed as the `adapter=` of search_hp_tip,
+    tip_accuracy_grid and tip_logits. Because it has no bias, adapter(f) = f best_keys^T is
+    the built-in affinity with cache_keys = best_keys.t(): the search after training needs
+    no Python adapter, and tip_adapter_f runs it that way."""
+    for name, x in (("lr", lr), ("beta", beta), ("alpha", alpha)):
+        if isinstance(x, (list, tuple, torch.Tensor)):
+            raise TypeError(f"Expected {name} as one number; fit_adapter_grid takes lists.")
+    fit = fit_adapter_grid(cache_keys, cache_values, clip_weights, train_views, train_labels,
+                           [lr], [beta], [alpha], **kwargs)
+    return _linear_from_keys(fit.best_keys[0], fit)
+
+
+def tip_adapter_f(cfg, cache_keys, cache_values, train_views, train_labels, test_features,
+                  test_labels, clip_weights):
+    """The whole Tip-Adapter-F recipe on cached features: train the keys with
+    cfg['tip_f'] = {lr, train_epoch, init_beta, init_alpha[, batch_size, weight_decay, eps,
+    seed]}, keep the best epoch on (test_features, test_labels), then search (beta, alpha)
+    with search_hp_tip on the best keys (as built-in cache keys: the adapter has no bias).
+    Prints the recipe's per-epoch lines from the history, read once at the end. Returns
+    (adapter, best_beta, best_alpha, fit)."""
+    tf = cfg.get('tip_f') if hasattr(cfg, 'get') else None
+    if not hasattr(tf, 'get'):
+        raise ValueError("cfg['tip_f'] must be a mapping with lr, train_epoch, init_beta and "
+                         "init_alpha.")
+    missing = [k for k in ('lr', 'train_epoch', 'init_beta', 'init_alpha') if k not in tf]
+    if missing:
+        raise ValueError(f"cfg['tip_f'] lacks {missing}.")
+    unknown = sorted(set(tf) - {'lr', 'train_epoch', 'init_beta', 'init_alpha', 'batch_size',
+                                'weight_decay', 'eps', 'seed'})
+    if unknown:
+        raise ValueError(f"cfg['tip_f'] has unknown keys {unknown}.")
+    if cfg['search_hp'] != True:   # noqa: E712 -- search_hp_tip's own comparison
+        raise ValueError("cfg['search_hp'] is not True: tip_adapter_f ends with search_hp_tip.")
+    beta_alpha_lists(cfg)
+    if test_features is None or test_labels is None:
+        raise ValueError("tip_adapter_f needs test_features and test_labels.")
+    lr, epochs = float(tf['lr']), tf['train_epoch']
+    fit = fit_adapter_grid(cache_keys, cache_values, clip_weights, train_views, train_labels,
+                           [lr], [tf['init_beta']], [tf['init_alpha']], epochs=epochs,
+                           batch_size=tf.get('batch_size', 256),
+                           weight_decay=tf.get('weight_decay', 0.01), eps=tf.get('eps', 1e-4),
+                           seed=tf.get('seed', 0), eval_features=test_features,
+                           eval_labels=test_labels)
+    spe, T, Nq = fit.steps_per_epoch, epochs * fit.steps_per_epoch, int(test_features.shape[0])
+    hist = fit.history[:, 0].cpu().view(epochs, spe, 2)             # the one host read
+    counts, best_epoch = fit.eval_counts[:, 0].cpu().tolist(), int(fit.best_epoch[0])
+    for e in range(epochs):
+        print('Train Epoch: {:} / {:}'.format(e, epochs))
+        correct = int(hist[e, :, 1].sum())
+        print('LR: {:.6f}, Acc: {:.4f} ({:}/{:}), Loss: {:.4f}'.format(
+            lr * cosine_lr_factor((e + 1) * spe + 1, T), correct / fit.n, correct, fit.n,
+            float(hist[e, :, 0].mean())))
+        print("**** Tip-Adapter-F's test accuracy: {:.2f}. ****\n".format(100 * counts[e] / Nq))
+    best = 100 * int(fit.best_count[0]) / Nq
+    print(f"**** After fine-tuning, Tip-Adapter-F's best test accuracy: {best:.2f}, at epoch: "
+          f"{best_epoch}. ****\n")
+    best_beta, best_alpha = search_hp_tip(cfg, fit.best_keys[0].t(), cache_values, test_features,
+                                          test_labels, clip_weights)
+    return _linear_from_keys(fit.best_keys[0], fit), best_beta, best_alpha, fit

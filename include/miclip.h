@@ -426,6 +426,50 @@ int miclip_tip_logits(const float* affinity, const int32_t* key_labels, const fl
                       int32_t Nq, int32_t Nk, int32_t C, float beta, float alpha, float* logits,
                       void* scratch, void* stream);
 
+/* ---- Tip-Adapter-F: training the cache keys on cached features, fp32 ----
+ * The fine-tuned variant of the cache classifier: the adapter is a bias-free
+ * Linear(E, Nk) initialised to the cache keys, adapter(f) = f keys^T, and only keys
+ * [Nk, E] train, by AdamW (betas 0.9 / 0.999, decoupled weight decay) under a cosine
+ * schedule that the caller folds into lr_factor. G configurations (lr, beta, alpha)
+ * train at once on the same batch; a configuration's result depends neither on G nor on
+ * its index. Limits: 1 <= n <= 2^24 cached rows, 1 <= b <= 4096 batch rows, 1 <= Nk <=
+ * 65536, E % 16 == 0 in [16, 1024], 1 <= C <= 1024, 1 <= G <= 64; step >= 1; lr_factor,
+ * weight_decay >= 0 and eps >= 0 finite. lr / betas / alphas [G] are DEVICE fp32 arrays
+ * that the host caller checks to be finite (miclip/tip.py does); labels [n] and key_labels
+ * [Nk] are DEVICE int32 in [0, C), checked by the host caller as for miclip_tip_grid.
+ * No float atomics and a fixed order for every float sum: bit-identical run to run.
+ * Nothing allocates or synchronises.
+ * scratch: miclip_tipf_scratch_bytes(b, Nk, E, C, G) bytes (0 outside the limits; b is
+ * the largest batch of the fit), 256-byte aligned. miclip_tipf_prepare sorts the key
+ * labels into it once per fit, before the first step. */
+int64_t miclip_tipf_scratch_bytes(int32_t b, int32_t Nk, int32_t E, int32_t C, int32_t G);
+int miclip_tipf_prepare(const int32_t* key_labels, int32_t Nk, int32_t C, void* scratch,
+                        void* stream);
+/* One step on the rows rows_host [b] (a HOST int64 array, every entry checked against
+ * [0, n) before any launch and staged through launch arguments: free on return) of F
+ * [n, E] (f_dtype MICLIP_F32 / FP16 / BF16), clip_logits [n, C] = 100 F W and labels [n]:
+ *   A = F_b keys_g^T, phi = exp(-(beta_g - beta_g A)), S[r, c] = sum of phi[r, k] over the
+ *   keys of class c in ascending k, loss = mean CE(clip_logits_b + alpha_g S, y_b),
+ *   dkeys = (alpha_g beta_g phi * gm[:, cls(k)])^T F_b with gm = (softmax - onehot) / b,
+ *   lr_t = lr[g] * lr_factor; keys *= 1 - lr_t * weight_decay; m, v as torch.optim.AdamW;
+ *   keys -= lr_t / (1 - 0.9^step) * m / (sqrt(v) / sqrt(1 - 0.999^step) + eps).
+ * keys / m / v [G, Nk, E] are updated in place. history [G, 2] = {mean CE, number of
+ * rows whose first argmax is the label} of the batch before the update. grad_out
+ * [G, Nk, E] receives dkeys, or is NULL. */
+int miclip_tipf_step(const void* F, int32_t f_dtype, int32_t n, const int64_t* rows_host,
+                     int32_t b, const int32_t* labels, const float* clip_logits,
+                     const int32_t* key_labels, float* keys, float* m, float* v, const float* lr,
+                     const float* betas, const float* alphas, int32_t Nk, int32_t E, int32_t C,
+                     int32_t G, float lr_factor, float weight_decay, float eps, int32_t step,
+                     float* history, float* grad_out, void* scratch, void* stream);
+/* The recipe's `if acc > best_acc` on the device. counts [>= epoch + 1, G] int32 holds
+ * the correct counts of the epochs so far (row e: epoch e). Where counts[epoch, g] is
+ * strictly greater than every earlier row's and than 0, best_keys[g] = keys[g],
+ * best_count[g] = counts[epoch, g], best_epoch[g] = epoch; otherwise nothing is written. */
+int miclip_tipf_keep_best(const int32_t* counts, int32_t epoch, const float* keys,
+                          float* best_keys, int32_t* best_count, int32_t* best_epoch, int32_t Nk,
+                          int32_t E, int32_t G, void* stream);
+
 /* ---- fine-tuning of the image tower's tail ----
  * FTOpenCLIP's training step (methods/PEFT_openclip.py:247-274) for
  * unlocked_groups 1 and 2 of lock_image_tower (:196-197): first the op-level
