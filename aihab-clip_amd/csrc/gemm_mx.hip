@@ -1015,6 +1015,10 @@ hipError_t gemm_mx(const void* A, const void* SA, const void* W, const void* SW,
                    void* C, void* CS, int M, int N, int K, int epi, int act, hipStream_t s,
                    int variant) {
   if (!A || !SA || !W || !SW || !C) return hipErrorInvalidValue;
+  // an activation the epilogue does not implement is refused, never replaced:
+  // epi 0 {none, QuickGELU, GELU}, epi 1 {none}, epi 5 those and the tanh form
+  if (act < ACT_NONE || act > (epi == 5 ? ACT_GELU_TANH : epi == 1 ? ACT_NONE : ACT_GELU))
+    return hipErrorInvalidValue;
   switch (epi) {
     case 0:   // fp16 store: act(acc + bias)
       if (act == ACT_NONE)

@@ -56,6 +56,8 @@ hipError_t quant_mx(int in_f16, const void* in, int R, int K, void* q, void* sc,
 // C = A[M,K] . W[N,K]^T with MX-fp8 operands (N % 256 == 0, K % 128 == 0).
 // epi 0: C fp16 = act(acc + bias); epi 1: C fp16 residual += acc + bias;
 // epi 5: C MX-fp8 data [M, N] + scale plane CS = MX(act(acc + bias)).
+// act: epi 0 none / QuickGELU / GELU, epi 1 none, epi 5 those and ACT_GELU_TANH;
+// anything else is refused. bias may be null for epi 0 and 5.
 // variant: 0 persistent where it applies (K >= 256), 1 one tile per workgroup,
 // 2 persistent only (bit-identical kernels; A/B)
 hipError_t gemm_mx(const void* A, const void* SA, const void* W, const void* SW, const float* bias,
