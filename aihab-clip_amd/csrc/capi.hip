@@ -1066,6 +1066,51 @@ int miclip_proto_scores(const float* x, const float* protos, const int32_t* owne
   return 0;
 }
 
+// the limits the two trimmed-centroid entry points share; false (and `why`) when one is broken
+static_assert(MICLIP_TRIM_MAX_CLASS_ROWS == kTrimMaxClassRows &&
+                  MICLIP_TRIM_MAX_ROUNDS == kTrimMaxRounds,
+              "include/miclip.h and csrc/kernels.h disagree on the trimmed-centroid limits");
+static bool trim_args_ok(int32_t K, int32_t N, std::string& why) {
+  if (K < 1 || K > 65535) why = "K must be in 1..65535, got " + std::to_string(K);
+  else if (N < 1 || N > MICLIP_TRIM_MAX_CLASS_ROWS)
+    why = "N must be in 1.." + std::to_string(MICLIP_TRIM_MAX_CLASS_ROWS) +
+          " (the largest supported class), got " + std::to_string(N);
+  return why.empty();
+}
+
+int miclip_segment_rank(const float* values, const int32_t* order, const int32_t* offsets,
+                        int32_t K, int32_t N, int32_t* rank_out, void* stream) {
+  const std::pair<const void*, const char*> ptrs[] = {
+      {values, "values"}, {order, "order"}, {offsets, "offsets"}, {rank_out, "rank_out"}};
+  for (const auto& a : ptrs)
+    if (!a.first) return fail(MICLIP_EINVAL, std::string("null argument: ") + a.second);
+  std::string why;
+  if (!trim_args_ok(K, N, why)) return fail(MICLIP_EINVAL, why);
+  MICLIP_HIP(segment_rank(values, order, offsets, K, N, rank_out, (hipStream_t)stream));
+  return 0;
+}
+
+int miclip_trimmed_centroids(const float* x, const int32_t* order, const int32_t* offsets,
+                             const int32_t* cls, const int32_t* drop, int32_t K, int32_t N,
+                             int32_t D, int32_t rounds, float eps, float* sums, float* centroids,
+                             uint8_t* keep, float* sims, int32_t* changed, void* stream) {
+  const std::pair<const void*, const char*> ptrs[] = {
+      {x, "x"}, {order, "order"}, {offsets, "offsets"}, {cls, "cls"}, {drop, "drop"},
+      {sums, "sums"}, {centroids, "centroids"}, {keep, "keep"}, {sims, "sims"},
+      {changed, "changed"}};
+  for (const auto& a : ptrs)
+    if (!a.first) return fail(MICLIP_EINVAL, std::string("null argument: ") + a.second);
+  std::string why;
+  if (!trim_args_ok(K, N, why)) return fail(MICLIP_EINVAL, why);
+  if (D < 1) return fail(MICLIP_EINVAL, "D must be >= 1, got " + std::to_string(D));
+  if (rounds < 1 || rounds > MICLIP_TRIM_MAX_ROUNDS)
+    return fail(MICLIP_EINVAL, "rounds must be in 1.." + std::to_string(MICLIP_TRIM_MAX_ROUNDS) +
+                                   ", got " + std::to_string(rounds));
+  MICLIP_HIP(trimmed_centroids(x, order, offsets, cls, drop, K, N, D, rounds, eps, sums,
+                               centroids, keep, sims, changed, (hipStream_t)stream));
+  return 0;
+}
+
 // the limits the two k-means entry points share; false (and `why`) when one is broken
 static bool kmeans_args_ok(int32_t D, int32_t Pn, int32_t k_max, std::string& why) {
   if (D < 1 || D > 1024) why = "D must be in 1..1024, got " + std::to_string(D);

@@ -174,6 +174,30 @@ hipError_t proto_scores(const float* x, const float* protos, const int32_t* owne
                         int P, int D, float* own_best, int32_t* own_arg, float* other_best,
                         hipStream_t s);
 
+// ---- trimmed class centroids (trim.hip), fp32 ----
+// Rank by counting costs sum n_k^2 compares, so the class size is bounded: the
+// largest supported class has kTrimMaxClassRows rows. The layout is device memory,
+// so the bound is enforced through N (no class is larger than N): N above it is
+// hipErrorInvalidValue before any launch. kTrimTile: (value, index) pairs staged in
+// LDS per step of the rank kernel (8 KiB).
+constexpr int kTrimTile = 1024;
+constexpr int kTrimMaxClassRows = 65536;
+constexpr int kTrimMaxRounds = 8;
+// rank_out[i] = #{j in class of i : (values[j], j) < (values[i], i)}, IEEE '<' on the
+// fp32 values (-0 and +0 tie), sample order; order / offsets as in class_centroids.
+// values must not hold NaN (a NaN ties with everything). K >= 1, 1 <= N <= kTrimMaxClassRows.
+hipError_t segment_rank(const float* values, const int32_t* order, const int32_t* offsets, int K,
+                        int N, int32_t* rank_out, hipStream_t s);
+// rounds (1..kTrimMaxRounds) of {sims = x_i . c[cls[i]]; keep = rank >= drop[class];
+// sums / centroids over the kept rows in ascending sample order} from the plain
+// centroid, all enqueued on s with no host read. drop [K] is clamped to 0..n_k-1 on the
+// device. keep uint8 [N], sims [N] (last round's), changed int32 [rounds] (flags flipped
+// per round, keep_0 = all ones), sums / centroids [K, D]. 1 <= K <= 65535, D >= 1.
+hipError_t trimmed_centroids(const float* x, const int32_t* order, const int32_t* offsets,
+                             const int32_t* cls, const int32_t* drop, int K, int N, int D,
+                             int rounds, float eps, float* sums, float* centroids,
+                             uint8_t* keep, float* sims, int32_t* changed, hipStream_t s);
+
 // ---- device k-means for the multi-prototype scorer (kmeans.hip), fp32 ----
 // Pn problems, one workgroup each: problem p clusters class prob_class[p]'s rows
 // (order / offsets as in class_centroids) into prob_k[p] <= k_max clusters; its

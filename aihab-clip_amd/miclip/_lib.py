@@ -47,6 +47,7 @@ EXPORTS = (
     "miclip_op_layernorm", "miclip_op_attention", "miclip_op_attention_q0", "miclip_op_im2col", "miclip_preprocess", "miclip_preprocess_aug",
     "miclip_row_norms", "miclip_class_centroids", "miclip_proto_scores",
     "miclip_kmeans_scratch_bytes", "miclip_kmeans_seed", "miclip_kmeans_lloyd",
+    "miclip_segment_rank", "miclip_trimmed_centroids",
     "miclip_tsne_scratch_bytes", "miclip_tsne_affinities", "miclip_tsne_run",
     "miclip_prolip_grad", "miclip_prolip_adam",
     "miclip_tip_scratch_bytes", "miclip_tip_keys", "miclip_tip_affinity", "miclip_tip_grid",
@@ -179,6 +180,9 @@ def load_library(path: str = None):
                                ctypes.c_int),
         "miclip_kmeans_lloyd": ([vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, vp,
                                  vp, vp, vp, vp], ctypes.c_int),
+        "miclip_segment_rank": ([vp, vp, vp, i32, i32, vp, vp], ctypes.c_int),
+        "miclip_trimmed_centroids": ([vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp,
+                                      vp, vp], ctypes.c_int),
         "miclip_tsne_scratch_bytes": ([i32], i64),
         "miclip_tsne_affinities": ([vp, i32, i32, i32, f32, vp, vp, vp, vp, vp], ctypes.c_int),
         "miclip_tsne_run": ([vp, i32, vp, vp, vp, i32, f32, f32, f32, f32, i32, vp, vp, vp],

@@ -8,6 +8,8 @@ kernels of csrc/scoring.hip through the C ABI:
 
   * row norms / re-normalisation      miclip_row_norms        (:229-247)
   * class centroids                   miclip_class_centroids  (:250-291)
+  * trimmed class centroids           miclip_trimmed_centroids (:250-257, the
+    (compute_centroids(trim_frac=))   reserved "trimmed-centroid support")
   * cosine to own centroid            miclip_proto_scores     (:293-383)
   * nearest own-class prototype and
     best other-class prototype        miclip_proto_scores     (:557-760)
@@ -31,6 +33,8 @@ from pathlib import Path
 from typing import Dict, List, Optional, Tuple
 
 import ctypes
+import math
+import numbers
 
 import numpy as np
 import pandas as pd
@@ -53,6 +57,11 @@ class CentroidResult:
     centroids: Dict[int, torch.Tensor]
     class_counts: Dict[int, int]
     dim: int
+    # set by compute_centroids(trim_frac=...) only; class_counts stays the full class size
+    trim_frac: Optional[float] = None
+    kept_counts: Optional[Dict[int, int]] = None
+    kept_mask: Optional[np.ndarray] = None          # bool [N] on the host, sample order
+    rounds_changed: Optional[List[int]] = None      # flags flipped in each trimming round
 
 
 @dataclass
@@ -159,16 +168,22 @@ def _class_centroids(x: torch.Tensor, inv: np.ndarray, K: int, eps: float):
     return cent, counts
 
 
+def _csr_layout(inv: np.ndarray, K: int, dev):
+    """The class layout every per-class kernel walks: (order, offsets) as device int32
+    and the host counts [K]. Class k's rows are order[offsets[k] .. offsets[k + 1]), in
+    ascending sample order (a stable sort of the class indices)."""
+    order = np.argsort(inv, kind="stable").astype(np.int32)
+    counts = np.bincount(inv, minlength=K)
+    offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+    return torch.from_numpy(order).to(dev), torch.from_numpy(offsets).to(dev), counts
+
+
 def _class_layout(x: torch.Tensor, inv: np.ndarray, K: int, eps: float):
     """_class_centroids plus the device class layout it was computed on:
     (centroids, counts, {"order", "offsets" (device int32), "sums" [K, D]})."""
     lib = _lib.load_library()
-    order = np.argsort(inv, kind="stable").astype(np.int32)
-    counts = np.bincount(inv, minlength=K)
-    offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
     dev = x.device
-    order_d = torch.from_numpy(order).to(dev)
-    off_d = torch.from_numpy(offsets).to(dev)
+    order_d, off_d, counts = _csr_layout(inv, K, dev)
     D = x.shape[1]
     sums = torch.empty(K, D, device=dev, dtype=torch.float32)
     cent = torch.empty(K, D, device=dev, dtype=torch.float32)
@@ -177,6 +192,93 @@ def _class_layout(x: torch.Tensor, inv: np.ndarray, K: int, eps: float):
                                               float(eps), _ptr(sums), _ptr(cent), _stream(dev)),
                    "miclip_class_centroids")
     return cent, counts, {"order": order_d, "offsets": off_d, "sums": sums}
+
+
+_TRIM_TILE, _TRIM_MAX_CLASS_ROWS, _TRIM_MAX_ROUNDS = 1024, 65536, 8   # limits of csrc/trim.hip
+
+
+def _segment_rank(values: torch.Tensor, order_d: torch.Tensor, off_d: torch.Tensor, K: int):
+    """miclip_segment_rank: 0-based rank of every row inside its class by the key
+    (value ascending, sample index ascending); int32 [N] in sample order."""
+    lib = _lib.load_library()
+    N, dev = values.shape[0], values.device
+    rank = torch.empty(N, device=dev, dtype=torch.int32)
+    with torch.cuda.device(dev):
+        _lib.check(lib.miclip_segment_rank(_ptr(values), _ptr(order_d), _ptr(off_d), K, N,
+                                           _ptr(rank), _stream(dev)), "miclip_segment_rank")
+    return rank
+
+
+def _trim_drop(counts, trim_frac: float) -> np.ndarray:
+    """drop[k] = floor(trim_frac * n_k), in Python float64 on the host."""
+    return np.asarray([int(math.floor(float(trim_frac) * int(n))) for n in counts], np.int32)
+
+
+def _trimmed_centroids(x: torch.Tensor, inv: np.ndarray, K: int, drop: np.ndarray, rounds: int,
+                       eps: float):
+    """miclip_trimmed_centroids on the class layout of `inv`: every round on the
+    device in one call. Returns device tensors {"centroids", "sums" [K, D], "keep"
+    uint8 [N], "sims" [N], "changed" int32 [rounds]} and the host "counts" [K]."""
+    lib = _lib.load_library()
+    N, D = x.shape
+    dev = x.device
+    order_d, off_d, counts = _csr_layout(inv, K, dev)
+    as_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.int32)).to(dev)   # noqa: E731
+    cls_d, drop_d = as_dev(inv), as_dev(drop)
+    out = {"sums": torch.empty(K, D, device=dev, dtype=torch.float32),
+           "centroids": torch.empty(K, D, device=dev, dtype=torch.float32),
+           "keep": torch.empty(N, device=dev, dtype=torch.uint8),
+           "sims": torch.empty(N, device=dev, dtype=torch.float32),
+           "changed": torch.empty(int(rounds), device=dev, dtype=torch.int32)}
+    with torch.cuda.device(dev):
+        _lib.check(lib.miclip_trimmed_centroids(
+            _ptr(x), _ptr(order_d), _ptr(off_d), _ptr(cls_d), _ptr(drop_d), K, N, D, int(rounds),
+            float(eps), _ptr(out["sums"]), _ptr(out["centroids"]), _ptr(out["keep"]),
+            _ptr(out["sims"]), _ptr(out["changed"]), _stream(dev)), "miclip_trimmed_centroids")
+    out["counts"] = counts
+    return out
+
+
+def _trim_groups(counts, limit: int) -> List[List[int]]:
+    """Consecutive classes packed into groups of at most `limit` rows each (a class is
+    never split; the caller has checked that none is larger than `limit`)."""
+    groups, rows = [[]], 0
+    for k, n in enumerate(counts):
+        if groups[-1] and rows + int(n) > limit:
+            groups.append([])
+            rows = 0
+        groups[-1].append(k)
+        rows += int(n)
+    return groups
+
+
+def _trimmed_centroids_grouped(x: torch.Tensor, inv: np.ndarray, K: int, drop: np.ndarray,
+                               rounds: int, eps: float, limit: int = _TRIM_MAX_CLASS_ROWS):
+    """_trimmed_centroids for any number of rows. One call takes at most `limit` rows, and
+    trimming a class touches that class's rows only, so a larger cache goes through one
+    call per group of _trim_groups, each on a gathered copy of its rows (ascending sample
+    order, so every sum keeps its order: the results are those of a single call, bit for
+    bit). Returns {"centroids" [K, D], "keep" uint8 [N], "changed" int32 [rounds]} on the
+    device and the host "counts"; nothing is read back."""
+    counts = np.bincount(inv, minlength=K)
+    groups = _trim_groups(counts, limit)
+    if len(groups) == 1:
+        return _trimmed_centroids(x, inv, K, drop, rounds, eps)
+    dev = x.device
+    cent = torch.empty(K, x.shape[1], device=dev, dtype=torch.float32)
+    keep = torch.empty(x.shape[0], device=dev, dtype=torch.uint8)
+    changed = torch.zeros(int(rounds), device=dev, dtype=torch.int32)
+    first = np.cumsum([0] + [len(g) for g in groups])
+    group_of = np.repeat(np.arange(len(groups)), [len(g) for g in groups])
+    for gi, g in enumerate(groups):
+        rows = np.flatnonzero(group_of[inv] == gi)            # ascending sample order
+        rows_d = torch.from_numpy(rows).to(dev)
+        out = _trimmed_centroids(x.index_select(0, rows_d).contiguous(), inv[rows] - first[gi],
+                                 len(g), drop[g[0]:g[-1] + 1], rounds, eps)
+        cent[g[0]:g[-1] + 1] = out["centroids"]
+        keep[rows_d] = out["keep"]
+        changed += out["changed"]
+    return {"centroids": cent, "keep": keep, "changed": changed, "counts": counts}
 
 
 def _proto_scores(x, protos, owner, cls, inv_nx=None, inv_np=None):
@@ -316,6 +418,7 @@ class SingleCentroidScorer:
         self.normalize_tol = float(normalize_tol)
         self.eps = float(eps)
         self._centroids: Optional[CentroidResult] = None
+        self._trimmed_centroids: Dict[Tuple[float, int], CentroidResult] = {}
         self._normalized_embeddings: Optional[torch.Tensor] = None
         if "ground_truth_num_label" in self.metadata.columns:
             meta_labels = torch.tensor(
@@ -346,9 +449,16 @@ class SingleCentroidScorer:
             self._normalized_embeddings = emb
         return self._normalized_embeddings
 
-    def compute_centroids(self, *, trim_frac: Optional[float] = None) -> CentroidResult:
+    def compute_centroids(self, *, trim_frac: Optional[float] = None,
+                          trim_rounds: int = 1) -> CentroidResult:
+        """Per-class normalised centroids. With trim_frac = f in [0, 0.5) the centroid
+        is trimmed (DESIGN "Trimmed class centroids"): trim_rounds times over, the
+        floor(f * n_k) rows of each class least similar to the current centroid (ties:
+        the lower sample index first) are left out and the centroid is re-formed from
+        the rest, all on the device (miclip_trimmed_centroids). The result also names
+        the kept rows; class_counts stays the full class size."""
         if trim_frac is not None:
-            raise NotImplementedError("trim_frac is not implemented yet (planned follow-up).")
+            return self._compute_trimmed_centroids(trim_frac, trim_rounds)
         if self._centroids is not None:
             return self._centroids
         emb = self._get_normalized_embeddings()
@@ -361,6 +471,43 @@ class SingleCentroidScorer:
             centroids={int(uniq[i]): cent[i] for i in range(K)},
             class_counts={int(uniq[i]): int(counts[i]) for i in range(K)}, dim=self.dim)
         return self._centroids
+
+    def _compute_trimmed_centroids(self, trim_frac, trim_rounds) -> CentroidResult:
+        if isinstance(trim_frac, bool) or not isinstance(trim_frac, numbers.Real) or \
+                not 0.0 <= float(trim_frac) < 0.5:
+            raise ValueError(f"trim_frac must be a real number with 0 <= trim_frac < 0.5, "
+                             f"got {trim_frac!r}.")
+        if isinstance(trim_rounds, bool) or not isinstance(trim_rounds, numbers.Integral) or \
+                not 1 <= int(trim_rounds) <= _TRIM_MAX_ROUNDS:
+            raise ValueError(f"trim_rounds must be an int in [1, {_TRIM_MAX_ROUNDS}], "
+                             f"got {trim_rounds!r}.")
+        key = (float(trim_frac), int(trim_rounds))
+        if key in self._trimmed_centroids:
+            return self._trimmed_centroids[key]
+        uniq, inv = self._classes()
+        K = int(uniq.numel())
+        if K == 0:
+            raise ValueError("No labels present to compute centroids.")
+        sizes = np.bincount(inv, minlength=K)
+        if int(sizes.max()) > _TRIM_MAX_CLASS_ROWS:
+            big = int(np.argmax(sizes))
+            raise ValueError(f"trim_frac supports classes of at most {_TRIM_MAX_CLASS_ROWS} "
+                             f"rows, class {int(uniq[big])} has {int(sizes[big])}.")
+        emb = self._get_normalized_embeddings()
+        drop = _trim_drop(sizes, key[0])
+        out = _trimmed_centroids_grouped(emb, inv, K, drop, key[1], self.eps)
+        # the one copy to the host: the keep flags and the per-round change counts
+        host = torch.cat([out["keep"].to(torch.int32), out["changed"]]).cpu().numpy()
+        kept_mask = host[:self.num_samples].astype(bool)
+        kept = np.bincount(inv[kept_mask], minlength=K)
+        cent, counts = out["centroids"], out["counts"]
+        res = CentroidResult(
+            centroids={int(uniq[i]): cent[i] for i in range(K)},
+            class_counts={int(uniq[i]): int(counts[i]) for i in range(K)}, dim=self.dim,
+            trim_frac=key[0], kept_counts={int(uniq[i]): int(kept[i]) for i in range(K)},
+            kept_mask=kept_mask, rounds_changed=[int(v) for v in host[self.num_samples:]])
+        self._trimmed_centroids[key] = res
+        return res
 
     def _frame(self):
         scores = self.metadata.copy().reset_index(drop=True)

@@ -250,6 +250,50 @@ int miclip_proto_scores(const float* x, const float* protos, const int32_t* owne
                         int32_t P, int32_t D, float* own_best, int32_t* own_arg,
                         float* other_best, void* stream);
 
+/* ---- trimmed class centroids, fp32 ----
+ * The "trimmed-centroid support" that compute_centroids(trim_frac=...) is reserved
+ * for (tools/outlier_cleaning.py:250-257). Mislabelled rows pull the plain mean
+ * towards themselves; a trimmed centroid drops the drop[k] rows of class k that
+ * are least similar to the class centroid and re-forms it from the rest:
+ *   c_0 = the centroid of miclip_class_centroids (same kernels, bit for bit);
+ *   round t = 1..rounds:
+ *     s_i   = x_i . c_{t-1}[cls[i]]           (fp32, a fixed summation order per row)
+ *     r_i   = rank of row i among ALL rows of its class by the key (s ascending,
+ *             sample index ascending); IEEE '<' on the fp32 values, so -0 and +0 tie
+ *     keep_t[i] = r_i >= drop[class]
+ *     c_t   = normalize(sum of the kept rows in ascending sample order / kept count)
+ *     changed[t-1] = #{i : keep_t[i] != keep_{t-1}[i]},  keep_0 = all ones.
+ * drop[k] = floor(trim_frac * n_k) is the caller's (an integer, computed on the
+ * host); the device clamps it to 0 .. n_k - 1, so a non-empty class keeps at least
+ * one row. With every drop[k] == 0 the centroids are bit-identical to
+ * miclip_class_centroids. There are no float atomics: results are bit-identical run
+ * to run. Ranking counts pairs (sum n_k^2 compares), so the largest supported class
+ * has MICLIP_TRIM_MAX_CLASS_ROWS rows; the layout is device memory, so the bound is
+ * enforced through N (no class is larger than N). All pointers are caller-owned
+ * device memory; the calls are stream-ordered, never synchronise and never allocate.
+ * Limits: 1 <= K <= 65535, 1 <= N <= MICLIP_TRIM_MAX_CLASS_ROWS, D >= 1,
+ * 1 <= rounds <= MICLIP_TRIM_MAX_ROUNDS, no NULL pointer; anything else is
+ * MICLIP_EINVAL with the argument named in miclip_last_error, before any launch.
+ * values / x must be free of NaN (a NaN ties with every value). */
+#define MICLIP_TRIM_MAX_CLASS_ROWS 65536
+#define MICLIP_TRIM_MAX_ROUNDS 8
+/* miclip_segment_rank (outlier_cleaning.py:250-257, the selection step on its own):
+ * rank_out[i] = #{j in the class of i : (values[j], j) < (values[i], i)} for the
+ * class layout order / offsets of miclip_class_centroids; values, rank_out: [N] in
+ * sample order. Within a class the ranks are a permutation of 0 .. n_k - 1. */
+int miclip_segment_rank(const float* values, const int32_t* order, const int32_t* offsets,
+                        int32_t K, int32_t N, int32_t* rank_out, void* stream);
+/* miclip_trimmed_centroids (outlier_cleaning.py:250-257): all `rounds` rounds in one
+ * call, with no host read in between. x [N, D]; cls int32 [N] = class index of each
+ * row (the inverse of order / offsets); drop int32 [K]. Outputs: sums [K, D] (the
+ * kept rows' sums of the last round), centroids [K, D] = c_rounds, keep uint8 [N] =
+ * keep_rounds, sims [N] = the similarities of the last round (against
+ * c_{rounds-1}), changed int32 [rounds]. */
+int miclip_trimmed_centroids(const float* x, const int32_t* order, const int32_t* offsets,
+                             const int32_t* cls, const int32_t* drop, int32_t K, int32_t N,
+                             int32_t D, int32_t rounds, float eps, float* sums, float* centroids,
+                             uint8_t* keep, float* sims, int32_t* changed, void* stream);
+
 /* ---- device k-means for the multi-prototype scorer, fp32 ----
  * Replace the per-class KMeans(n_init, max_iter).fit of compute_prototypes
  * (tools/outlier_cleaning.py:511-541) by two launches over a problem table: a
