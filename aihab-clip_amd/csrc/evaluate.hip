@@ -34,8 +34,9 @@
 // Nothing is indexed by such a label or by a missing pick.
 #include <math.h>
 
-#include "common.h"
 #include "kernels.h"
+#include "launch.h"
+#include "mfma_f32.h"
 
 namespace miclip {
 
@@ -67,17 +68,6 @@ struct EvalArgs {
   float scale;
 };
 
-template <typename T>
-MICLIP_DEV float4 load4(const T* p) {
-  if constexpr (sizeof(T) == 4) {
-    return *(const float4*)p;
-  } else {
-    const u32x2 raw = *(const u32x2*)p;
-    const T* e = (const T*)&raw;
-    return float4{to_f<T>(e[0]), to_f<T>(e[1]), to_f<T>(e[2]), to_f<T>(e[3])};
-  }
-}
-
 // embed.hip's mfma_chunks for four 16-class tiles at once, with the x element type as
 // a parameter (widened exactly in the load). Per tile it is the same MFMA chain --
 // ascending k chunks, x, y, z, w inside a chunk -- and the same fmaf chain for n2, so
@@ -98,7 +88,7 @@ MICLIP_DEV void mfma_chunks4(const T* __restrict__ xp, const float* __restrict__
       for (int s2 = 0; s2 < 4; ++s2) bv[t][s2] = wrow[(size_t)(16 * ch + s2) * ldw + col[t]];
     }
   };
-  const auto chunk = [&](const float4& a, const float bv[4][4]) {
+  const auto chunk = [&](const f32x4& a, const float bv[4][4]) {
 #pragma unroll
     for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, bv[t][0], acc[t], 0, 0, 0);
 #pragma unroll
@@ -111,7 +101,7 @@ MICLIP_DEV void mfma_chunks4(const T* __restrict__ xp, const float* __restrict__
   };
   int ch = c0;
   for (; ch + 2 <= c1; ch += 2) {   // the loads of two chunks are issued together
-    const float4 a0 = load4<T>(xp + 16 * ch), a1 = load4<T>(xp + 16 * (ch + 1));
+    const f32x4 a0 = load4<T>(xp + 16 * ch), a1 = load4<T>(xp + 16 * (ch + 1));
     float b0[4][4], b1[4][4];
     loadw(ch, b0);
     loadw(ch + 1, b1);
@@ -119,18 +109,11 @@ MICLIP_DEV void mfma_chunks4(const T* __restrict__ xp, const float* __restrict__
     chunk(a1, b1);
   }
   if (ch < c1) {
-    const float4 a0 = load4<T>(xp + 16 * ch);
+    const f32x4 a0 = load4<T>(xp + 16 * ch);
     float b0[4][4];
     loadw(ch, b0);
     chunk(a0, b0);
   }
-}
-
-// sum over the 16 lanes that share a row, fixed butterfly
-MICLIP_DEV float sum16(float v) {
-#pragma unroll
-  for (int o = 1; o < 16; o <<= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 // The top 3 of v[0 .. n) by the 16 lanes (sub = 0 .. 15) that share the row: value
@@ -426,12 +409,9 @@ __global__ __launch_bounds__(256) void eval_finalise_kernel(const float* __restr
 template <typename T, bool LOGITS_IN>
 hipError_t launch_rows(const EvalArgs& a, const L2MapArg& map, hipStream_t s) {
   const EvalLds lay(a.C, a.num_l2, a.l2_mode >= kEvalL2Sum);
-  if (lay.total > 64 * 1024) {   // at most 160,640 B (C = num_l2 = 1024) of the 160 KiB
-    const hipError_t attr = hipFuncSetAttribute((const void*)eval_rows_kernel<T, LOGITS_IN>,
-                                                hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                160 * 1024);
-    if (attr != hipSuccess) return attr;
-  }
+  // at most 160,640 B (C = num_l2 = 1024) of the 160 KiB
+  const hipError_t attr = lds_opt_in((const void*)eval_rows_kernel<T, LOGITS_IN>, lay.total);
+  if (attr != hipSuccess) return attr;
   hipLaunchKernelGGL((eval_rows_kernel<T, LOGITS_IN>), dim3((a.B + 15) / 16), dim3(256), lay.total,
                      s, a, map);
   return hipGetLastError();
@@ -457,8 +437,7 @@ hipError_t eval_batch(int f_dtype, const void* f, const float* tw, const int64_t
   if (!eval_shape_ok(B, E, C, num_l2, l2_mode, logits_in) || !labels || !state || !row_loss ||
       ((uintptr_t)state & 7))
     return hipErrorInvalidValue;
-  if (logits_in ? !logits : (!f || !tw || ((uintptr_t)f & 15) ||
-                             (f_dtype != kIn32 && f_dtype != kF16 && f_dtype != kBF16)))
+  if (logits_in ? !logits : (!f || !tw || ((uintptr_t)f & 15) || !in_dtype_ok(f_dtype)))
     return hipErrorInvalidValue;
   if ((l2_mode != kEvalL2None) != (l3_to_l2_host != nullptr)) return hipErrorInvalidValue;
   L2MapArg map;
@@ -472,15 +451,11 @@ hipError_t eval_batch(int f_dtype, const void* f, const float* tw, const int64_t
   const EvalArgs a = {f, tw, labels, logits, row_loss, row_pred, row_top3, row_top3_prob,
                       l2_pred, l2_top3, l2_logits, (unsigned long long*)state, B, E, C, num_l2,
                       l2_mode, scale};
-  hipError_t e;
-  if (logits_in)
-    e = launch_rows<float, true>(a, map, s);
-  else if (f_dtype == kIn32)
-    e = launch_rows<float, false>(a, map, s);
-  else if (f_dtype == kF16)
-    e = launch_rows<_Float16, false>(a, map, s);
-  else
-    e = launch_rows<__bf16, false>(a, map, s);
+  const hipError_t e =
+      logits_in ? launch_rows<float, true>(a, map, s)
+                : dispatch_in_dtype(f_dtype, [&](auto tag) {
+                    return launch_rows<typename decltype(tag)::type, false>(a, map, s);
+                  });
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(eval_finalise_kernel, dim3(1), dim3(256), 0, s, row_loss, B,
                      (unsigned long long*)state);

@@ -30,15 +30,15 @@
 //   * ft_grad_rows: the same step on images picked out of a cache of trunk outputs. The
 //     only two readers of x (ft_ln_fwd_kernel, ft_add_rows_kernel) take a row map, null
 //     for ft_grad, so the batch is never gathered into a buffer of its own; the host's
-//     indices are checked, then staged from the arguments of ft_stage_rows_kernel.
+//     indices are checked, then staged from launch arguments (stage_rows, launch.h).
 //
 // Determinism: every accumulation runs in ascending row order inside one wave,
 // slices are added in index order, there are no atomics; the maximum behind the
 // scale is order-independent.
 #include <math.h>
 
-#include "common.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace miclip {
 
@@ -228,8 +228,6 @@ __global__ void ft_fold_kernel(const float* __restrict__ part, int ntiles,
   stats[0] = ce;
   stats[1] = ok;
 }
-
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 }  // namespace
 
@@ -628,17 +626,6 @@ __global__ __launch_bounds__(256) void ft_add_rows_kernel(const float* __restric
   out[e] = a[e] + to_f<TI>(x[i * stride + k]);
 }
 
-// dst[i] = c.v[i], i < n: a piece of a host array, carried by the launch's own arguments
-constexpr int kStageChunk = 256;
-struct FtRowChunk {
-  int64_t v[kStageChunk];
-};
-__global__ __launch_bounds__(kStageChunk) void ft_stage_rows_kernel(FtRowChunk c,
-                                                                    int64_t* __restrict__ dst,
-                                                                    int n) {
-  if ((int)threadIdx.x < n) dst[threadIdx.x] = c.v[threadIdx.x];
-}
-
 __global__ __launch_bounds__(256) void ft_add_kernel(const float* __restrict__ a,
                                                      const float* __restrict__ b,
                                                      float* __restrict__ out, size_t numel) {
@@ -996,12 +983,7 @@ hipError_t ft_grad_rows(int dtype, int x_dtype, const void* x_cache, int64_t cac
   // the index area follows ft_grad's own scratch; each piece travels as launch arguments, so
   // the caller's array is free on return and the stream is never waited for
   int64_t* rows = (int64_t*)((char*)scratch + ft_scratch_bytes(B, N, W, E, C, dh));
-  for (int b0 = 0; b0 < B; b0 += kStageChunk) {
-    const int n = B - b0 < kStageChunk ? B - b0 : kStageChunk;
-    FtRowChunk c;
-    for (int i = 0; i < kStageChunk; ++i) c.v[i] = i < n ? rows_host[b0 + i] : 0;
-    hipLaunchKernelGGL(ft_stage_rows_kernel, dim3(1), dim3(kStageChunk), 0, s, c, rows + b0, n);
-  }
+  stage_rows(rows, B, s, [&](int b) { return rows_host[b]; });
   FT_TRY(hipGetLastError());
   return ft_grad_any(dtype, x_dtype, x_cache, rows, labels, tw, params, B, N, W, E, C, dh, act,
                      scale, groups, grads, scratch, stats, y_out, s);

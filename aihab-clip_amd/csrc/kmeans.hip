@@ -41,15 +41,15 @@
 // skipped: n_iter = -1 (lloyd), picks = -1 (seed), nothing else written.
 #include <math.h>
 
-#include "common.h"
 #include "kernels.h"
+#include "launch.h"
+#include "mfma_f32.h"
 
 namespace miclip {
 
 namespace {
 
 constexpr int kSlots = 16;   // centre slots per problem (k <= 16)
-constexpr int kKmPad = 4;    // LDS row stride = Dp + 4 floats (prolip.hip's kLdsPad)
 
 struct KmProblem {
   const int32_t* ord;   // the class's rows
@@ -169,28 +169,6 @@ __global__ __launch_bounds__(256) void kmeans_seed_kernel(
   }
 }
 
-template <bool VEC>
-MICLIP_DEV f32x4 km_load4(const float* row, int col, int D) {
-  if constexpr (VEC) {   // D % 4 == 0: the 4 columns are all inside or all outside
-    return col < D ? *(const f32x4*)(row + col) : f32x4{0.f, 0.f, 0.f, 0.f};
-  } else {
-    f32x4 v;
-    v.x = col + 0 < D ? row[col + 0] : 0.f;
-    v.y = col + 1 < D ? row[col + 1] : 0.f;
-    v.z = col + 2 < D ? row[col + 2] : 0.f;
-    v.w = col + 3 < D ? row[col + 3] : 0.f;
-    return v;
-  }
-}
-
-MICLIP_DEV f32x4 km_mfma4(const f32x4& a, const f32x4& b, f32x4 acc) {
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, acc, 0, 0, 0);
-  return acc;
-}
-
 // E-step of one workgroup: labels[r] = argmin_j cn[j] - 2 x_r . C_j. With TRACK the
 // cluster counts and the "some label changed" flag are updated too.
 template <bool VEC, bool TRACK>
@@ -209,10 +187,10 @@ MICLIP_DEV void km_estep(const float* __restrict__ x, const KmProblem& q, int D,
     const float* crow = C + i * ld + 4 * g;
     for (int c0 = 0; c0 < Dp; c0 += 16) {
       const f32x4 bv = *(const f32x4*)(crow + c0);
-      const f32x4 a0 = km_load4<VEC>(row0, c0 + 4 * g, D);
-      const f32x4 a1 = km_load4<VEC>(row1, c0 + 4 * g, D);
-      acc[0] = km_mfma4(a0, bv, acc[0]);
-      acc[1] = km_mfma4(a1, bv, acc[1]);
+      const f32x4 a0 = load4_clip<VEC>(row0, c0 + 4 * g, D);
+      const f32x4 a1 = load4_clip<VEC>(row1, c0 + 4 * g, D);
+      acc[0] = mfma4(a0, bv, acc[0]);
+      acc[1] = mfma4(a1, bv, acc[1]);
     }
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -263,7 +241,7 @@ __global__ __launch_bounds__(256) void kmeans_lloyd_kernel(
     return;
   }
   const int n = q.n, k = q.k;
-  const int Dp = (D + 15) & ~15, ld = Dp + kKmPad;
+  const int Dp = (D + 15) & ~15, ld = Dp + kLdsPad;
   float* C = (float*)smem;            // [16][ld] centres, columns >= D and slots >= k zero
   float* S = C + kSlots * ld;         // [16][ld] cluster sums, then the new means
   float* cn = S + kSlots * ld;        // [16] |c_j|^2
@@ -474,13 +452,10 @@ hipError_t launch_lloyd(const float* x, const int32_t* order, const int32_t* off
                         float* scratch, float* centres, int32_t* labels, float* inertia,
                         int32_t* n_iter, int32_t* strict, int32_t* counts, hipStream_t s) {
   const int Dp = (D + 15) & ~15;
-  const size_t lds = (size_t)(2 * kSlots * (Dp + kKmPad) + 2 * kSlots + 16) * sizeof(float);
-  if (lds > 64 * 1024) {   // at most 131,776 B (D = 1024) of the 160 KiB
-    const hipError_t attr = hipFuncSetAttribute((const void*)kmeans_lloyd_kernel<VEC>,
-                                                hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                160 * 1024);
-    if (attr != hipSuccess) return attr;
-  }
+  const size_t lds = (size_t)(2 * kSlots * (Dp + kLdsPad) + 2 * kSlots + 16) * sizeof(float);
+  // at most 131,776 B (D = 1024) of the 160 KiB
+  const hipError_t attr = lds_opt_in((const void*)kmeans_lloyd_kernel<VEC>, lds);
+  if (attr != hipSuccess) return attr;
   hipLaunchKernelGGL(kmeans_lloyd_kernel<VEC>, dim3(Pn), dim3(256), lds, s, x, order, offsets, D,
                      prob_class, prob_k, prob_off, tol, max_iter, scratch, centres, labels,
                      inertia, n_iter, strict, counts);

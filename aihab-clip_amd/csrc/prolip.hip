@@ -38,51 +38,13 @@
 // launch B: zero operands behind every real row of the ascending k chain).
 #include <math.h>
 
-#include "common.h"
 #include "kernels.h"
+#include "launch.h"
+#include "mfma_f32.h"
 
 namespace miclip {
 
 namespace {
-
-constexpr int kLdsPad = 4;   // row stride = width + 4 floats: 16 rows of float4 hit 16 bank groups
-
-template <typename T>
-MICLIP_DEV f32x4 load4(const T* p) {
-  if constexpr (sizeof(T) == 4) {
-    return *(const f32x4*)p;
-  } else {
-    const u32x2 raw = *(const u32x2*)p;
-    const T* e = (const T*)&raw;
-    return f32x4{to_f<T>(e[0]), to_f<T>(e[1]), to_f<T>(e[2]), to_f<T>(e[3])};
-  }
-}
-
-MICLIP_DEV f32x4 mfma4(const f32x4& a, const f32x4& b, f32x4 acc) {
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, acc, 0, 0, 0);
-  return acc;
-}
-
-// One wave's 16 x 16 fp32 product over nch chunks of 16 k, ascending. Lane (i =
-// lane & 15, g = lane >> 4): fa(ch) = A[row i][16 ch + 4g + s], fb(ch) = B[16 ch +
-// 4g + s][col i] for s = 0..3 (the same k permutation on both operands, as in
-// embed.hip's mfma_chunks). The lane ends with rows 4g .. 4g+3 of column i. The
-// loads of two chunks are issued together; the accumulation order is unchanged.
-template <typename FA, typename FB>
-MICLIP_DEV f32x4 mfma_k(int nch, FA fa, FB fb) {
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  int ch = 0;
-  for (; ch + 2 <= nch; ch += 2) {
-    const f32x4 a0 = fa(ch), b0 = fb(ch), a1 = fa(ch + 1), b1 = fb(ch + 1);
-    acc = mfma4(a0, b0, acc);
-    acc = mfma4(a1, b1, acc);
-  }
-  if (ch < nch) acc = mfma4(fa(ch), fb(ch), acc);
-  return acc;
-}
 
 // Error-free addition of p into the pair (hi, lo): hi + lo + p is preserved exactly
 // (Knuth's TwoSum; no multiplications, so contraction cannot touch it).
@@ -93,7 +55,7 @@ MICLIP_DEV void two_sum(f32x4& hi, f32x4& lo, const f32x4 p) {
   hi = s;
 }
 
-// mfma_k with a compensated accumulator, for the two products whose rounding is
+// mfma_k (mfma_f32.h) with a compensated accumulator, for the two products whose rounding is
 // multiplied by `scale` on its way into the softmax (Z = X P and f W): every MFMA
 // (4 k) starts from zero and its result is added to a running (hi, lo) pair without
 // error, so the only roundings left are inside the 4-term MFMA sums, at the size of
@@ -122,13 +84,6 @@ MICLIP_DEV f32x4 mfma_k_comp(int nch, FA fa, FB fb) {
   two_sum(h0, l0, h2);
   two_sum(h0, l0, h3);
   return h0 + ((l0 + l1) + (l2 + l3));
-}
-
-// sum over the 16 lanes that share a row (lanes 16 r' .. 16 r' + 15 of a wave), fixed butterfly
-MICLIP_DEV float sum16(float v) {
-#pragma unroll
-  for (int o = 1; o < 16; o <<= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 template <typename T>
@@ -363,12 +318,9 @@ hipError_t launch_grad(const void* x, const int64_t* labels, const float* W, con
                        hipStream_t s) {
   const int Cp = (C + 15) & ~15;
   const size_t lds = (size_t)(16 * (E + kLdsPad) + 16 * (Cp + kLdsPad) + 64) * sizeof(float);
-  if (lds > 64 * 1024) {   // at most 131,840 B (E = C = 1024) of the 160 KiB
-    const hipError_t attr = hipFuncSetAttribute((const void*)prolip_grad_kernel<T>,
-                                                hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                160 * 1024);
-    if (attr != hipSuccess) return attr;
-  }
+  // at most 131,840 B (E = C = 1024) of the 160 KiB
+  const hipError_t attr = lds_opt_in((const void*)prolip_grad_kernel<T>, lds);
+  if (attr != hipSuccess) return attr;
   hipLaunchKernelGGL(prolip_grad_kernel<T>, dim3((n + 15) / 16, G), dim3(256), lds, s,
                      (const T*)x, labels, P, W, dZ, part, n, D, E, C, scale);
   return hipGetLastError();
@@ -382,12 +334,12 @@ hipError_t prolip_grad(int x_dtype, const void* x, const int64_t* labels, const 
                        const float* P, float* dZ, float* part, int n, int D, int E, int C, int G,
                        float scale, hipStream_t s) {
   if (!prolip_shape_ok(n, D, E, G) || C < 1 || C > 1024 || ((uintptr_t)x & 15) ||
-      (x_dtype != kIn32 && x_dtype != kF16 && x_dtype != kBF16))
+      !in_dtype_ok(x_dtype))
     return hipErrorInvalidValue;
-  if (x_dtype == kIn32) return launch_grad<float>(x, labels, W, P, dZ, part, n, D, E, C, G, scale, s);
-  if (x_dtype == kF16)
-    return launch_grad<_Float16>(x, labels, W, P, dZ, part, n, D, E, C, G, scale, s);
-  return launch_grad<__bf16>(x, labels, W, P, dZ, part, n, D, E, C, G, scale, s);
+  return dispatch_in_dtype(x_dtype, [&](auto tag) {
+    return launch_grad<typename decltype(tag)::type>(x, labels, W, P, dZ, part, n, D, E, C, G,
+                                                     scale, s);
+  });
 }
 
 hipError_t prolip_adam(int x_dtype, const void* x, const float* dZ, const float* P0, float* P,
@@ -396,21 +348,17 @@ hipError_t prolip_adam(int x_dtype, const void* x, const float* dZ, const float*
                        int E, int G, float lr_factor, float lambda_div, int step, float eps,
                        hipStream_t s) {
   if (!prolip_shape_ok(n, D, E, G) || step < 1 || !(lambda_div > 0.f) || !(eps >= 0.f) ||
-      (x_dtype != kIn32 && x_dtype != kF16 && x_dtype != kBF16))
+      !in_dtype_ok(x_dtype))
     return hipErrorInvalidValue;
   // bias corrections in double, as torch's Python scalars (1 - beta ** step)
   const AdamArgs a = {lr_factor, lambda_div, (float)(1.0 - pow(0.9, (double)step)),
                       (float)sqrt(1.0 - pow(0.999, (double)step)), eps};
   const dim3 grid((E + 31) / 32, (D + 31) / 32, G);
-  if (x_dtype == kIn32)
-    hipLaunchKernelGGL(prolip_adam_kernel<float>, grid, dim3(256), 0, s, (const float*)x, dZ, P0,
-                       P, m, v, lr, lam, mse_part, n, D, E, a);
-  else if (x_dtype == kF16)
-    hipLaunchKernelGGL(prolip_adam_kernel<_Float16>, grid, dim3(256), 0, s, (const _Float16*)x,
-                       dZ, P0, P, m, v, lr, lam, mse_part, n, D, E, a);
-  else
-    hipLaunchKernelGGL(prolip_adam_kernel<__bf16>, grid, dim3(256), 0, s, (const __bf16*)x, dZ,
-                       P0, P, m, v, lr, lam, mse_part, n, D, E, a);
+  dispatch_in_dtype(x_dtype, [&](auto tag) {
+    typedef typename decltype(tag)::type T;
+    hipLaunchKernelGGL(prolip_adam_kernel<T>, grid, dim3(256), 0, s, (const T*)x, dZ, P0, P, m, v,
+                       lr, lam, mse_part, n, D, E, a);
+  });
   hipLaunchKernelGGL(prolip_fold_kernel, dim3(G), dim3(64), 0, s, grad_part, (n + 15) / 16,
                      mse_part, prolip_adam_tiles(D, E), n, history);
   return hipGetLastError();

@@ -17,27 +17,20 @@
 // encoder (N x P x D with P = classes x <= 6 prototypes) and HBM-bound on the
 // embeddings read; 64 samples x 64 prototypes per workgroup step, 4 x 4
 // outputs per thread from LDS.
-#include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdint.h>
 
+#include "common.h"
 #include "kernels.h"
 
 namespace miclip {
 namespace {
-
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 __global__ __launch_bounds__(64) void row_norms_kernel(const float* __restrict__ x, int D,
                                                        float* __restrict__ norms) {
   const float* row = x + (size_t)blockIdx.x * D;
   float s = 0.f;
   for (int d = threadIdx.x; d < D; d += 64) s = fmaf(row[d], row[d], s);
-  s = wsum(s);
+  s = wave_sum(s);
   if (threadIdx.x == 0) norms[blockIdx.x] = sqrtf(s);
 }
 
@@ -78,7 +71,7 @@ __global__ __launch_bounds__(64) void centroid_kernel(const float* __restrict__ 
     o[d] = m;
     n2 = fmaf(m, m, n2);
   }
-  const float nrm = fmaxf(sqrtf(wsum(n2)), eps);
+  const float nrm = fmaxf(sqrtf(wave_sum(n2)), eps);
   for (int d = threadIdx.x; d < D; d += 64) o[d] = o[d] / nrm;
 }
 

@@ -2,8 +2,7 @@
 // (methods/utils.py:23-62 build_cache_model, :64-94 search_hp_tip) on the device.
 // All arithmetic is fp32 on exactly widened inputs (fp16 / bf16 / fp32 in the load);
 // the three matrix products run on the f32-input MFMA (v_mfma_f32_16x16x4_f32: exact
-// fp32 products, one fp32 fmaf chain per output element in a fixed order of k: chunks of
-// 16 ascending, inside a chunk k = s, 4 + s, 8 + s, 12 + s for s = 0..3).
+// fp32 products, one fp32 fmaf chain per output element in mfma_f32.h's fixed order of k).
 //
 //   * tip_keys_kernel, grid ceil(Nk / 16), one 16-row tile of keys per workgroup:
 //     for every view v in ascending order Z = x_v proj (MFMA), f = Z / max(|Z|, 1e-12)
@@ -35,61 +34,18 @@
 // there are no float atomics. Nothing allocates or synchronises.
 #include <math.h>
 
-#include "common.h"
 #include "kernels.h"
+#include "launch.h"
+#include "mfma_f32.h"
 
 namespace miclip {
 
 namespace {
 
-constexpr int kLdsPad = 4;      // row stride = width + 4 floats (as prolip.hip)
 constexpr int kTipTile = 4096;  // sorted affinities staged per pass of tip_grid_kernel
 constexpr int kTipRows = 8;     // query rows per workgroup of tip_grid_kernel
 constexpr int kTipItems = 1024; // (class, beta) and (beta, alpha) items per workgroup
 constexpr int kTipBetas = 512;  // betas per workgroup
-
-template <typename T>
-MICLIP_DEV f32x4 load4(const T* p) {
-  if constexpr (sizeof(T) == 4) {
-    return *(const f32x4*)p;
-  } else {
-    const u32x2 raw = *(const u32x2*)p;
-    const T* e = (const T*)&raw;
-    return f32x4{to_f<T>(e[0]), to_f<T>(e[1]), to_f<T>(e[2]), to_f<T>(e[3])};
-  }
-}
-
-MICLIP_DEV f32x4 mfma4(const f32x4& a, const f32x4& b, f32x4 acc) {
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, acc, 0, 0, 0);
-  return acc;
-}
-
-// One wave's 16 x 16 fp32 product over nch chunks of 16 k, chunks ascending (prolip.hip's
-// mfma_k). Lane (i = lane & 15, g = lane >> 4): fa(ch) = A[row i][16 ch + 4g + s],
-// fb(ch) = B[16 ch + 4g + s][col i], s = 0..3; the lane ends with rows 4g .. 4g+3 of
-// column i.
-template <typename FA, typename FB>
-MICLIP_DEV f32x4 mfma_k(int nch, FA fa, FB fb) {
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  int ch = 0;
-  for (; ch + 2 <= nch; ch += 2) {
-    const f32x4 a0 = fa(ch), b0 = fb(ch), a1 = fa(ch + 1), b1 = fb(ch + 1);
-    acc = mfma4(a0, b0, acc);
-    acc = mfma4(a1, b1, acc);
-  }
-  if (ch < nch) acc = mfma4(fa(ch), fb(ch), acc);
-  return acc;
-}
-
-// sum over the 16 lanes that share a row, fixed butterfly
-MICLIP_DEV float sum16(float v) {
-#pragma unroll
-  for (int o = 1; o < 16; o <<= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 template <typename T>
 __global__ __launch_bounds__(256) void tip_keys_kernel(
@@ -299,17 +255,13 @@ __global__ __launch_bounds__(256) void tip_grid_kernel(
   }
 }
 
-bool tip_dtype_ok(int dtype) { return dtype == kIn32 || dtype == kF16 || dtype == kBF16; }
-
-size_t tip_order_bytes(int Nk) { return ((size_t)Nk * 4 + 255) & ~(size_t)255; }
+size_t tip_order_bytes(int Nk) { return align256((size_t)Nk * 4); }
 
 hipError_t tip_sort(const int32_t* key_labels, int Nk, int C, void* scratch, hipStream_t s) {
   const size_t lds = 1024 * sizeof(int32_t) + (((size_t)Nk * 2 + 15) & ~(size_t)15);
-  if (lds > 64 * 1024) {   // at most 135,168 B (Nk = 65536) of the 160 KiB
-    const hipError_t attr = hipFuncSetAttribute(
-        (const void*)tip_sort_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (attr != hipSuccess) return attr;
-  }
+  // at most 135,168 B (Nk = 65536) of the 160 KiB
+  const hipError_t attr = lds_opt_in((const void*)tip_sort_kernel, lds);
+  if (attr != hipSuccess) return attr;
   int32_t* order = (int32_t*)scratch;
   int32_t* offsets = (int32_t*)((char*)scratch + tip_order_bytes(Nk));
   hipLaunchKernelGGL(tip_sort_kernel, dim3(1), dim3(1024), lds, s, key_labels, Nk, C, order,
@@ -321,11 +273,9 @@ template <typename T>
 hipError_t launch_keys(const void* const* views, const float* proj, float* keys, int Nk, int Wv,
                        int E, int A, hipStream_t s) {
   const size_t lds = (size_t)16 * (E + kLdsPad) * sizeof(float);
-  if (lds > 64 * 1024) {   // 65,792 B at E = 1024
-    const hipError_t attr = hipFuncSetAttribute(
-        (const void*)tip_keys_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (attr != hipSuccess) return attr;
-  }
+  // 65,792 B at E = 1024
+  const hipError_t attr = lds_opt_in((const void*)tip_keys_kernel<T>, lds);
+  if (attr != hipSuccess) return attr;
   hipLaunchKernelGGL(tip_keys_kernel<T>, dim3((Nk + 15) / 16), dim3(256), lds, s, views, proj,
                      keys, Nk, Wv, E, A);
   return hipGetLastError();
@@ -356,32 +306,28 @@ hipError_t tip_sort_keys(const int32_t* key_labels, int Nk, int C, void* scratch
 
 size_t tip_scratch_bytes(int Nq, int Nk, int E, int C, int nb, int na) {
   if (tip_bad_arg(kTipAll, Nq, Nk, E, C, nb, na)) return 0;
-  return tip_order_bytes(Nk) + (((size_t)(C + 1) * 4 + 255) & ~(size_t)255);
+  return tip_order_bytes(Nk) + align256((size_t)(C + 1) * 4);
 }
 
 hipError_t tip_keys(int x_dtype, const void* const* views, int A, const float* proj, float* keys,
                     int Nk, int Wv, int E, hipStream_t s) {
-  if (!tip_dtype_ok(x_dtype) || tip_bad_arg(kTipNk | kTipE, 0, Nk, E, 0, 0, 0) || A < 1 || A > 1024 ||
+  if (!in_dtype_ok(x_dtype) || tip_bad_arg(kTipNk | kTipE, 0, Nk, E, 0, 0, 0) || A < 1 || A > 1024 ||
       Wv < 16 || Wv > 65536 || Wv % 16)
     return hipErrorInvalidValue;
-  if (x_dtype == kIn32) return launch_keys<float>(views, proj, keys, Nk, Wv, E, A, s);
-  if (x_dtype == kF16) return launch_keys<_Float16>(views, proj, keys, Nk, Wv, E, A, s);
-  return launch_keys<__bf16>(views, proj, keys, Nk, Wv, E, A, s);
+  return dispatch_in_dtype(x_dtype, [&](auto tag) {
+    return launch_keys<typename decltype(tag)::type>(views, proj, keys, Nk, Wv, E, A, s);
+  });
 }
 
 hipError_t tip_affinity(int f_dtype, const void* F, const float* keys, float* aff, int Nq, int Nk,
                         int E, float scale, hipStream_t s) {
-  if (!tip_dtype_ok(f_dtype) || tip_bad_arg(kTipNq | kTipNk | kTipE, Nq, Nk, E, 0, 0, 0)) return hipErrorInvalidValue;
+  if (!in_dtype_ok(f_dtype) || tip_bad_arg(kTipNq | kTipNk | kTipE, Nq, Nk, E, 0, 0, 0)) return hipErrorInvalidValue;
   const dim3 grid((Nq + 15) / 16, (Nk + 63) / 64);
-  if (f_dtype == kIn32)
-    hipLaunchKernelGGL(tip_affinity_kernel<float>, grid, dim3(256), 0, s, (const float*)F, keys,
-                       aff, Nq, Nk, E, scale);
-  else if (f_dtype == kF16)
-    hipLaunchKernelGGL(tip_affinity_kernel<_Float16>, grid, dim3(256), 0, s, (const _Float16*)F,
-                       keys, aff, Nq, Nk, E, scale);
-  else
-    hipLaunchKernelGGL(tip_affinity_kernel<__bf16>, grid, dim3(256), 0, s, (const __bf16*)F, keys,
-                       aff, Nq, Nk, E, scale);
+  dispatch_in_dtype(f_dtype, [&](auto tag) {
+    typedef typename decltype(tag)::type T;
+    hipLaunchKernelGGL(tip_affinity_kernel<T>, grid, dim3(256), 0, s, (const T*)F, keys, aff, Nq,
+                       Nk, E, scale);
+  });
   return hipGetLastError();
 }
 

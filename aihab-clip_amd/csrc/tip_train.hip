@@ -2,11 +2,10 @@
 // of G independent configurations (lr, beta, alpha) per call. The adapter is a bias-free
 // Linear(E, Nk) initialised to the cache keys, so adapter(f) = f K^T and only K [Nk, E]
 // trains. All arithmetic is fp32 on exactly widened inputs (F fp32 / fp16 / bf16); both
-// products run on the f32-input MFMA (v_mfma_f32_16x16x4_f32), in tip.hip's k order
-// (chunks of 16 ascending; inside a chunk k = s, 4 + s, 8 + s, 12 + s for s = 0..3).
+// products run on the f32-input MFMA (v_mfma_f32_16x16x4_f32), in mfma_f32.h's k order.
 //
 // For the b batch rows named by the row map (F_b, Z_b, y_b are rows of F, Z, labels):
-//   * tipf_stage_rows_kernel: the host row map, already checked against [0, n), travels
+//   * stage_rows (launch.h): the host row map, already checked against [0, n), travels
 //     in launch arguments (256 indices per launch) into the scratch; no gathered copy of
 //     F is formed and the caller's array is free on return.
 //   * tipf_forward_kernel, grid (ceil(b / 16), ceil(Nk / 64), G), one 16 x 16 tile per
@@ -40,74 +39,19 @@
 // the load and masked on the store. Nothing allocates or synchronises.
 #include <math.h>
 
-#include "common.h"
 #include "kernels.h"
+#include "launch.h"
+#include "mfma_f32.h"
 
 namespace miclip {
 
 namespace {
-
-constexpr int kLdsPad = 4;        // row stride = width + 4 floats (as prolip.hip)
-constexpr int kStageRows = 256;   // row-map indices per staging launch
-
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-template <typename T>
-MICLIP_DEV f32x4 load4(const T* p) {
-  if constexpr (sizeof(T) == 4) {
-    return *(const f32x4*)p;
-  } else {
-    const u32x2 raw = *(const u32x2*)p;
-    const T* e = (const T*)&raw;
-    return f32x4{to_f<T>(e[0]), to_f<T>(e[1]), to_f<T>(e[2]), to_f<T>(e[3])};
-  }
-}
-
-MICLIP_DEV f32x4 mfma4(const f32x4& a, const f32x4& b, f32x4 acc) {
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, acc, 0, 0, 0);
-  return acc;
-}
-
-// tip.hip's mfma_k: one wave's 16 x 16 product over nch chunks of 16 k, chunks ascending.
-// Lane (i = lane & 15, g = lane >> 4): fa(ch) = A[row i][16 ch + 4g + s], fb(ch) =
-// B[16 ch + 4g + s][col i], s = 0..3; the lane ends with rows 4g .. 4g+3 of column i.
-template <typename FA, typename FB>
-MICLIP_DEV f32x4 mfma_k(int nch, FA fa, FB fb) {
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  int ch = 0;
-  for (; ch + 2 <= nch; ch += 2) {
-    const f32x4 a0 = fa(ch), b0 = fb(ch), a1 = fa(ch + 1), b1 = fb(ch + 1);
-    acc = mfma4(a0, b0, acc);
-    acc = mfma4(a1, b1, acc);
-  }
-  if (ch < nch) acc = mfma4(fa(ch), fb(ch), acc);
-  return acc;
-}
-
-// sum over the 16 lanes that share a row, fixed butterfly
-MICLIP_DEV float sum16(float v) {
-#pragma unroll
-  for (int o = 1; o < 16; o <<= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // torch.topk's order: NaN above every number, the lower index first among equals
 MICLIP_DEV bool ranks_above(float v, int c, float best, int arg) {
   if (v != v) return best == best || c < arg;
   if (best != best) return false;
   return v > best || (v == best && c < arg);
-}
-
-struct TipfRowChunk {
-  int32_t v[kStageRows];
-};
-__global__ __launch_bounds__(kStageRows) void tipf_stage_rows_kernel(TipfRowChunk c,
-                                                                     int32_t* __restrict__ dst,
-                                                                     int n) {
-  if ((int)threadIdx.x < n) dst[threadIdx.x] = c.v[threadIdx.x];
 }
 
 template <typename T>
@@ -342,8 +286,6 @@ size_t tipf_layout(void* scratch, int b, int Nk, int C, int G, TipfScratch* out)
   return at;
 }
 
-bool tipf_dtype_ok(int dtype) { return dtype == kIn32 || dtype == kF16 || dtype == kBF16; }
-
 template <typename T>
 hipError_t tipf_launch(const void* F, const int32_t* labels, const float* Z,
                        const int32_t* key_labels, float* K, float* m, float* v, const float* lrs,
@@ -353,11 +295,9 @@ hipError_t tipf_launch(const void* F, const int32_t* labels, const float* Z,
   hipLaunchKernelGGL(tipf_forward_kernel<T>, dim3((b + 15) / 16, (Nk + 63) / 64, G), dim3(256), 0,
                      s, (const T*)F, t.rows, K, betas, t.phi, b, Nk, E);
   const size_t lds = (size_t)(16 * (C + kLdsPad) + 32) * sizeof(float);
-  if (lds > 64 * 1024) {   // 65,920 B at C = 1024
-    const hipError_t attr = hipFuncSetAttribute(
-        (const void*)tipf_loss_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (attr != hipSuccess) return attr;
-  }
+  // 65,920 B at C = 1024
+  const hipError_t attr = lds_opt_in((const void*)tipf_loss_kernel, lds);
+  if (attr != hipSuccess) return attr;
   hipLaunchKernelGGL(tipf_loss_kernel, dim3((b + 15) / 16, G), dim3(256), lds, s, t.phi, t.rows,
                      t.order, t.offsets, Z, labels, alphas, t.gm, t.part, b, Nk, C);
   hipLaunchKernelGGL(tipf_adamw_kernel<T>, dim3((Nk + 63) / 64, (E + 63) / 64, G), dim3(256), 0, s,
@@ -395,7 +335,7 @@ hipError_t tipf_step(int f_dtype, const void* F, int n, const int64_t* rows_host
                      const float* alphas, int Nk, int E, int C, int G, float lr_factor,
                      float weight_decay, float eps, int step, float* history, float* grad_out,
                      void* scratch, hipStream_t s) {
-  if (!tipf_dtype_ok(f_dtype) || tipf_bad_arg(n, b, Nk, E, C, G) || !rows_host || !scratch ||
+  if (!in_dtype_ok(f_dtype) || tipf_bad_arg(n, b, Nk, E, C, G) || !rows_host || !scratch ||
       ((uintptr_t)scratch & 255) || ((uintptr_t)F & 15) || ((uintptr_t)K & 15) || step < 1 ||
       !isfinite(lr_factor) || !(weight_decay >= 0.f) || !isfinite(weight_decay) ||
       !(eps >= 0.f) || !isfinite(eps))
@@ -404,24 +344,15 @@ hipError_t tipf_step(int f_dtype, const void* F, int n, const int64_t* rows_host
     if (rows_host[r] < 0 || rows_host[r] >= n) return hipErrorInvalidValue;
   TipfScratch t;
   tipf_layout(scratch, b, Nk, C, G, &t);
-  for (int r0 = 0; r0 < b; r0 += kStageRows) {
-    const int cnt = b - r0 < kStageRows ? b - r0 : kStageRows;
-    TipfRowChunk c;
-    for (int q = 0; q < kStageRows; ++q) c.v[q] = q < cnt ? (int32_t)rows_host[r0 + q] : 0;
-    hipLaunchKernelGGL(tipf_stage_rows_kernel, dim3(1), dim3(kStageRows), 0, s, c, t.rows + r0,
-                       cnt);
-  }
+  stage_rows(t.rows, b, s, [&](int r) { return (int32_t)rows_host[r]; });   // n <= 2^24
   // bias corrections in double, as torch's Python scalars (1 - beta ** step)
   const AdamWArgs a = {lr_factor, weight_decay, (float)(1.0 - pow(0.9, (double)step)),
                        (float)sqrt(1.0 - pow(0.999, (double)step)), eps};
-  if (f_dtype == kIn32)
-    return tipf_launch<float>(F, labels, Z, key_labels, K, m, v, lrs, betas, alphas, b, Nk, E, C,
-                              G, a, history, grad_out, t, s);
-  if (f_dtype == kF16)
-    return tipf_launch<_Float16>(F, labels, Z, key_labels, K, m, v, lrs, betas, alphas, b, Nk, E,
-                                 C, G, a, history, grad_out, t, s);
-  return tipf_launch<__bf16>(F, labels, Z, key_labels, K, m, v, lrs, betas, alphas, b, Nk, E, C,
-                             G, a, history, grad_out, t, s);
+  return dispatch_in_dtype(f_dtype, [&](auto tag) {
+    return tipf_launch<typename decltype(tag)::type>(F, labels, Z, key_labels, K, m, v, lrs, betas,
+                                                     alphas, b, Nk, E, C, G, a, history, grad_out,
+                                                     t, s);
+  });
 }
 
 hipError_t tipf_keep_best(const int32_t* counts, int epoch, const float* keys, float* best_keys,

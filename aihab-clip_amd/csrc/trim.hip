@@ -23,10 +23,9 @@
 // pair in the same order, so the centroids are bit-identical to class_centroids.
 // No float atomics: two runs are bit-identical. drop is clamped on the device to
 // 0 .. n_k - 1, so every non-empty class keeps at least one row.
-#include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdint.h>
 
+#include "common.h"
 #include "kernels.h"
 
 namespace miclip {
@@ -39,12 +38,6 @@ struct __attribute__((aligned(8))) RankKey {
   float s;
   int32_t idx;
 };
-
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 __device__ __forceinline__ int clamp_drop(int drop, int n) {
   return drop < 0 ? 0 : (drop > n - 1 ? (n > 0 ? n - 1 : 0) : drop);
@@ -64,7 +57,7 @@ __global__ __launch_bounds__(64) void own_sim_kernel(const float* __restrict__ x
   const float* c = cent + (size_t)k * D;
   float s = 0.f;
   for (int d = threadIdx.x; d < D; d += 64) s = fmaf(row[d], c[d], s);
-  s = wsum(s);
+  s = wave_sum(s);
   if (threadIdx.x == 0) sims[i] = s;
 }
 
@@ -228,7 +221,7 @@ __global__ __launch_bounds__(64) void trim_centroid_kernel(const float* __restri
     o[d] = m;
     n2 = fmaf(m, m, n2);
   }
-  const float nrm = fmaxf(sqrtf(wsum(n2)), eps);
+  const float nrm = fmaxf(sqrtf(wave_sum(n2)), eps);
   for (int d = threadIdx.x; d < D; d += 64) o[d] = o[d] / nrm;
 }
 

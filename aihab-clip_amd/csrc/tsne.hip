@@ -39,8 +39,8 @@
 // Non-finite input: every loop is bounded by N or a constant; no index comes from data.
 #include <math.h>
 
-#include "common.h"
 #include "kernels.h"
+#include "mfma_f32.h"
 
 namespace miclip {
 
@@ -69,28 +69,6 @@ MICLIP_DEV double block_sum_f64(double v, double* red) {
   return s;
 }
 
-template <bool VEC>
-MICLIP_DEV f32x4 ts_load4(const float* row, int col, int D) {
-  if constexpr (VEC) {   // D % 4 == 0: the 4 columns are all inside or all outside
-    return col < D ? *(const f32x4*)(row + col) : f32x4{0.f, 0.f, 0.f, 0.f};
-  } else {
-    f32x4 v;
-    v.x = col + 0 < D ? row[col + 0] : 0.f;
-    v.y = col + 1 < D ? row[col + 1] : 0.f;
-    v.z = col + 2 < D ? row[col + 2] : 0.f;
-    v.w = col + 3 < D ? row[col + 3] : 0.f;
-    return v;
-  }
-}
-
-MICLIP_DEV f32x4 ts_mfma4(const f32x4& a, const f32x4& b, f32x4 acc) {
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, acc, 0, 0, 0);
-  return acc;
-}
-
 // A workgroup owns a 64 x 64 block of dist, each of its 4 waves a 32 x 32 quarter
 // (2 x 2 MFMA tiles). Rows past N are clamped for the loads and masked at the store.
 // nrm[i] = |x_i|.
@@ -108,12 +86,12 @@ __global__ __launch_bounds__(256) void tsne_dist_kernel(const float* __restrict_
                      {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}};
   for (int c0 = 0; c0 < D; c0 += 16) {
     const int col = c0 + 4 * g;
-    const f32x4 a0 = ts_load4<VEC>(ar[0], col, D), a1 = ts_load4<VEC>(ar[1], col, D);
-    const f32x4 b0 = ts_load4<VEC>(br[0], col, D), b1 = ts_load4<VEC>(br[1], col, D);
-    acc[0][0] = ts_mfma4(a0, b0, acc[0][0]);
-    acc[0][1] = ts_mfma4(a0, b1, acc[0][1]);
-    acc[1][0] = ts_mfma4(a1, b0, acc[1][0]);
-    acc[1][1] = ts_mfma4(a1, b1, acc[1][1]);
+    const f32x4 a0 = load4_clip<VEC>(ar[0], col, D), a1 = load4_clip<VEC>(ar[1], col, D);
+    const f32x4 b0 = load4_clip<VEC>(br[0], col, D), b1 = load4_clip<VEC>(br[1], col, D);
+    acc[0][0] = mfma4(a0, b0, acc[0][0]);
+    acc[0][1] = mfma4(a0, b1, acc[0][1]);
+    acc[1][0] = mfma4(a1, b0, acc[1][0]);
+    acc[1][1] = mfma4(a1, b1, acc[1][1]);
   }
 #pragma unroll
   for (int hm = 0; hm < 2; ++hm)
