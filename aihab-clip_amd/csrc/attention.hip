@@ -29,6 +29,7 @@
 //     half padding (zero V columns, never stored).
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -1543,6 +1544,17 @@ hipError_t attn_launch_plain(const void* qkv, void* out, int B, int N, int H, hi
   return hipGetLastError();
 }
 
+// Heads per workgroup so that one round of workgroups over `slots` covers all heads, and
+// the grid that then serves them
+struct OneRound {
+  int hpw, grid;
+};
+inline OneRound one_round(int heads, int slots) {
+  int hpw = (heads + slots - 1) / slots;
+  hpw = hpw < 1 ? 1 : hpw;
+  return OneRound{hpw, (heads + hpw - 1) / hpw};
+}
+
 template <typename T, bool CAUSAL>
 hipError_t attn_launch(const void* qkv, void* out, int B, int N, int H, int dh, hipStream_t s,
                        int variant) {
@@ -1561,17 +1573,8 @@ hipError_t attn_launch(const void* qkv, void* out, int B, int N, int H, int dh, 
         if (e != hipSuccess) return e;
         a80p = true;
       }
-      static int ncu80 = [] {
-        int d = 0, n = 0;
-        if (hipGetDevice(&d) != hipSuccess ||
-            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d) != hipSuccess)
-          n = 256;
-        return n;
-      }();
-      const int heads = B * H;
-      int hpw = (heads + ncu80 - 1) / ncu80;
-      hpw = hpw < 1 ? 1 : hpw;
-      const int grid = (heads + hpw - 1) / hpw;
+      const OneRound r = one_round(B * H, cu_count());
+      const int hpw = r.hpw, grid = r.grid;
       hipLaunchKernelGGL((attention80p_kernel<T>), dim3(grid), dim3(512), lds80p, s, (const T*)qkv,
                          (T*)out, B, N, H, hpw, 1.0f / sqrtf(80.f), attn_prio());
       return hipGetLastError();
@@ -1616,17 +1619,8 @@ hipError_t attn_launch(const void* qkv, void* out, int B, int N, int H, int dh, 
       if (e != hipSuccess) return e;
       x8_attr = true;
     }
-    static int ncu8 = [] {
-      int d = 0, n = 0;
-      if (hipGetDevice(&d) != hipSuccess ||
-          hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d) != hipSuccess)
-        n = 256;
-      return n;
-    }();
-    const int heads = B * H, slots = 2 * ncu8;
-    int hpw = (heads + slots - 1) / slots;
-    hpw = hpw < 1 ? 1 : hpw;
-    const int grid = (heads + hpw - 1) / hpw;
+    const OneRound r = one_round(B * H, 2 * cu_count());
+    const int hpw = r.hpw, grid = r.grid;
     hipLaunchKernelGGL((attention_x8_kernel<T>), dim3(grid), dim3(512), lds_x8, s, (const T*)qkv,
                        (T*)out, B, N, H, Npad, hpw, 0.125f, attn_prio());
     return hipGetLastError();
@@ -1646,24 +1640,15 @@ hipError_t attn_launch(const void* qkv, void* out, int B, int N, int H, int dh, 
       }
       attr_set = true;
     }
-    // one round of workgroups over the CUs at the occupancy LDS allows
-    static int ncu = [] {
-      int d = 0, n = 0;
-      if (hipGetDevice(&d) != hipSuccess ||
-          hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d) != hipSuccess)
-        n = 256;
-      return n;
-    }();
     // split the last chunk's key tiles over the other waves when it holds 1-2 queries
     const int nvalid = N - 32 * (nchunks - 1);
     const bool split = !CAUSAL && nchunks >= 5 && nvalid <= 2 && variant == 4;
     const int waves = split ? nchunks - 1 : nchunks;
     const size_t lds_all = 2 * lds + (split ? (size_t)2 * waves * nvalid * 66 * 4 : 0);
     const int per_cu = (int)((160 * 1024) / lds_all) < 1 ? 1 : (int)((160 * 1024) / lds_all);
-    const int heads = B * H, slots = ncu * per_cu;
-    int hpw = (heads + slots - 1) / slots;
-    hpw = hpw < 1 ? 1 : hpw;
-    const int grid = (heads + hpw - 1) / hpw;
+    // one round of workgroups over the CUs at the occupancy LDS allows
+    const OneRound r = one_round(B * H, cu_count() * per_cu);
+    const int hpw = r.hpw, grid = r.grid;
     if (split)
       hipLaunchKernelGGL((attention_pipe_kernel<T, CAUSAL, true>), dim3(grid), dim3(waves * 64),
                          lds_all, s, (const T*)qkv, (T*)out, B, N, H, Npad, hpw, 0.125f,

@@ -25,7 +25,9 @@
 
 #include "../../include/miclip.h"
 #include "common.h"
+#include "gemm_plan.h"
 #include "kernels.h"
+#include "launch.h"
 
 using namespace miclip;
 
@@ -1757,6 +1759,21 @@ int miclip_op_gemm_splitk(int32_t dtype, const void* A, const void* W, const flo
   } else {
     return fail(MICLIP_EINVAL, "unknown epilogue");
   }
+  return 0;
+}
+
+int miclip_gemm_plan(int32_t M, int32_t N, int32_t K, int32_t epi, int32_t variant, int32_t sk,
+                     int32_t ncu, int32_t out[8]) {
+  if (!out) return fail(MICLIP_EINVAL, "null argument: out");
+  if (epi < 0 || epi > 6) return fail(MICLIP_EINVAL, "unknown epilogue");
+  if (ncu < 0) return fail(MICLIP_EINVAL, "ncu: expected 0 (this device) or a CU count");
+  // TrAcc<Epi> (epilogue.h): the dtype store, the fp16 residual, the folded-LN store
+  const bool tracc = epi == 0 || epi == 4 || epi == 5;
+  GemmPlan p;
+  if (!plan_gemm(M, N, K, variant, sk, true, tracc, epi == 6, ncu ? ncu : cu_count(), &p))
+    return fail(MICLIP_EINVAL, "the GEMM launcher refuses this shape / variant / sk");
+  const int32_t v[8] = {p.kernel, p.grid, p.block, p.gm, p.ntm_dp, p.wgs, p.wide, 0};
+  for (int i = 0; i < 8; ++i) out[i] = v[i];
   return 0;
 }
 

@@ -24,7 +24,9 @@
 // positional-embedding add (clip/model.py:217-221).
 #include "common.h"
 #include "epilogue.h"
+#include "gemm_plan.h"
 #include "kernels.h"
+#include "launch.h"
 
 #include <cstdlib>
 #include <type_traits>
@@ -1681,243 +1683,64 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(const T* __restrict__ A,
   if (wr == 0) lds_barrier();   // balance the stagger barrier
 }
 
-// Kernel variants and schedule switches are chosen by the op-level `variant`
-// argument only (miclip_op_gemm: A/B benches); the model path runs variant 0,
-// which picks by problem size. The library reads no environment variables.
-// Tile-row group of the 256x256 kernel's grouped order (default 4; a variant >=
-// 1000 carries another in its thousands digit).
-constexpr int gemm_group() { return 4; }
-
-int cu_count() {
-  static int ncu = [] {
-    int d = 0, n = 0;
-    if (hipGetDevice(&d) != hipSuccess ||
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d) != hipSuccess || n <= 0)
-      n = 256;
-    return n;
-  }();
-  return ncu;
-}
-
-// kGemmNoTail: every row in 256x256 tiles, no row-tail split (A/B benches).
-constexpr int kGemmNoTail = 1 << 16;
-// kGemmTailFirst: tail workgroups interleaved with the first tiles
-// (gemm256_kernel, block roles)
-constexpr int kGemmTailFirst = 1 << 17;
-// kGemmStagger: 8-us round stagger, see gemm256_kernel
-constexpr int kGemmStagger = 1 << 18;
-// kGemmTrAccOff: the persistent kernel's fp32 row-staging epilogue instead of the
-// transposed-accumulator one for EpiStore / EpiStoreLN (A/B)
-constexpr int kGemmTrAccOff = 1 << 21;
-
-// Split of a 256x256 launch into whole rounds of tiles plus a row tail
-// (gemm_tail_wg). The tile-rows kept in tiles are the largest multiple of
-// ncu / gcd(ntn, ncu) -- the tile count is then a whole number of rounds --
-// provided at most 256 rows are left over; otherwise every row stays in tiles.
-struct TailPlan {
-  int ntm_dp, wgs, wide;
-};
-
-
-TailPlan plan_tail(int M, int N, int TM = 256) {
-  const int ntm = (M + TM - 1) / TM, ntn = N / 256, ncu = cu_count();
-  int a = ntn, b = ncu;
-  while (b) {
-    const int t = a % b;
-    a = b;
-    b = t;
-  }
-  const int step = ncu / a;
-  const int ntm_dp = ntm / step * step;
-  const int rows = M - ntm_dp * TM;
-  if (ntm_dp == 0 || rows <= 0 || rows > 256 || N % 64) return TailPlan{ntm, 0, 0};
-  // gemm_tail_wg tasks: 32 x 128 or 16 x 64, whichever ends sooner: the tail
-  // adds (tasks per workgroup) x (task time) to the launch, and a wide task
-  // takes ~1.5x a narrow one (in-kernel stamps, K = 1024: 19.6k vs 12.8k cycles;
-  // ViT-L/14 QKV at M = 32896: 384 narrow tasks = 2 per workgroup -> 96 wide
-  // ones, the tail's share of the launch 5.2 -> 2.1 %)
-  const int wide_tasks = (rows + 31) / 32 * (N / 128);
-  const int narrow_tasks = (rows + 15) / 16 * (N / 64);
-  const int wide_cost = (wide_tasks + ncu - 1) / ncu * 3;
-  const int narrow_cost = (narrow_tasks + ncu - 1) / ncu * 2;
-  if (N % 128 == 0 && wide_cost < narrow_cost) return TailPlan{ntm_dp, wide_tasks, 1};
-  return TailPlan{ntm_dp, narrow_tasks, 0};
-}
-
-// Row plan of the persistent kernel: where a launch of 256-row tiles is a single
-// partial round, the smallest tile height whose tiles still fit one round -- 128
-// rows, else 192 -- otherwise 256-row tiles with the row tail (plan_tail). Every
-// plan gives each row the same MFMA k order and epilogue functor, so the choice (a
-// function of M) never changes a result bit. Measured op-level, interleaved rounds
-// (profiles/r06/rows/rows_ops.jsonl): a 128- / 192-row tile costs 0.69-0.81 / 0.84-0.90
-// of a 256-row one (its DMA pieces per K-tile shrink to 3/4 / 7/8, not 1/2 / 3/4),
-// so splitting into two rounds or adding tail tasks to one round of smaller tiles
-// never paid (ViT-L/14 at 32 images, out-proj: 192-row 0.0255 ms, 128-row + tail
-// 0.0294, two rounds of 128-row 0.0378, 256-row 0.0284).
-struct RowPlan {
-  int rb;
-  TailPlan tp;
-};
-
-RowPlan choose_rows(int M, int N) {
-  const int ncu = cu_count(), ntn = N / 256;
-  if (((M + 255) / 256) * ntn <= ncu) {
-    if (((M + 127) / 128) * ntn <= ncu) return RowPlan{2, TailPlan{(M + 127) / 128, 0, 0}};
-    if (((M + 191) / 192) * ntn <= ncu) return RowPlan{3, TailPlan{(M + 191) / 192, 0, 0}};
-  }
-  return RowPlan{4, plan_tail(M, N, 256)};
-}
-
-bool gemm_shape_ok(int M, int N, int K) {
-  return M >= 1 && N >= 128 && K >= BK && N % 128 == 0 && K % BK == 0;
-}
-
+// Which kernel runs, with which tile height, grid and row-tail split, is plan_gemm's
+// decision (gemm_plan.h); this only carries it out, one launch per GemmKernel. The
+// cases an epilogue has no kernel for stay behind `if constexpr`: plan_gemm never
+// names them for such an epilogue.
 template <typename T, class Epi>
 hipError_t launch(const void* A, const void* W, int M, int N, int K, Epi epi, hipStream_t s,
                   int variant = 0, float* skws = nullptr, int sk = 1) {
-  if (!gemm_shape_ok(M, N, K)) return hipErrorInvalidValue;
-  if (sk > 1) {   // split-K (small M, long K: the CLS-only last block), deterministic
-    if (!skws || K % (sk * BK) || N % 128) return hipErrorInvalidValue;
-    const int tiles = ((M + 127) / 128) * (N / 128);
-    hipLaunchKernelGGL((gemm_nt_splitk_kernel<T>), dim3(tiles, sk), dim3(256), 0, s,
-                       (const T*)A, (const T*)W, M, N, K, K / sk, skws);
-    const int64_t n4 = (int64_t)M * (N / 4);
-    hipLaunchKernelGGL((splitk_reduce_kernel<Epi>), dim3((unsigned)((n4 + 255) / 256)), dim3(256),
-                       0, s, (const float*)skws, sk, M, N, epi);
-    return hipGetLastError();
-  }
-  const bool notail = variant & kGemmNoTail;
-  const bool tail_first = variant & kGemmTailFirst;
-  const bool stagger = variant & kGemmStagger;
-  const bool variant_tracc_off = variant & kGemmTrAccOff;
-  variant &= ~(kGemmNoTail | kGemmTailFirst | kGemmStagger | kGemmTrAccOff);
-  const int gm = variant >= 1000 ? variant / 1000 : gemm_group();
-  variant %= 1000;
-  const bool env_variant = false;   // an explicit variant never falls back silently
-  if (variant != 0 && variant != 128 && variant != 256 && variant != 257 && variant != 258 &&
-      variant != 259 && variant != 260 && variant != 3 && variant != 192 && variant != 129 &&
-      variant != 130)
+  GemmPlan p;
+  if (!plan_gemm(M, N, K, variant, sk, skws != nullptr, TrAcc<Epi>::value, IsPatch<Epi>::value,
+                 cu_count(), &p))
     return hipErrorInvalidValue;
-  // default for full-size problems: the persistent staggered kernel (variant
-  // 259; same-process A/B vs 258 on the ViT-L/14 shapes: QKV +1 %, out-proj +9 %,
-  // c_fc +1 %, c_proj +1 %)
-  // (from half a round of 256x256 tiles up: ViT-B/32 bs=128 QKV 225 tiles 0.047 ->
-  // 0.028 ms, out-proj bs=256 150 tiles 0.051 -> 0.028 ms vs the 128x128 kernel)
-  const bool by_size = variant == 0;   // the launcher picks (not an explicit A/B variant)
-  if (variant == 0 && !IsPatch<Epi>::value && N % 256 == 0 && K >= 128 &&
-      2 * ((M + 255) / 256) * (N / 256) >= cu_count())
-    variant = 259;
-  // Smaller row tiles (gemm256s_kernel RB 3 / 2, transposed-accumulator epilogues)
-  // where 256-row tiles leave CUs idle for part of the launch (choose_rows; e.g.
-  // ViT-B/32 bs=256 out-proj / c_proj: 150 -> 201 tiles of 192 rows on 256 CUs;
-  // ViT-L/14 at 32 images, M = 8224, N = 1024: 132 tiles of 256 rows -> 256 of 128
-  // plus the 32-row tail). The persistent kernel also takes launches below half a
-  // round of 256-row tiles when 128-row tiles fill one (at 16 images). Variants 192
-  // / 129 / 130 force 192-row tiles / 128-row tiles / 128-row tiles + row tail.
-  if constexpr (TrAcc<Epi>::value && !IsPatch<Epi>::value) {
-    const bool small_ok = by_size && N % 256 == 0 && K >= 128 &&
-                          2 * ((M + 127) / 128) * (N / 256) >= cu_count();
-    if ((variant == 259 || variant == 192 || variant == 129 || variant == 130 || small_ok) &&
-        N % 256 == 0 && K >= 128 && !variant_tracc_off) {
-      RowPlan rp{4, TailPlan{}};
-      if (variant == 192)
-        rp = RowPlan{3, TailPlan{(M + 191) / 192, 0, 0}};
-      else if (variant == 129)
-        rp = RowPlan{2, TailPlan{(M + 127) / 128, 0, 0}};
-      else if (variant == 130)
-        rp = RowPlan{2, plan_tail(M, N, 128)};
-      else if (by_size)
-        rp = choose_rows(M, N);
-      if (rp.rb != 4) {
-        const int ndp = rp.tp.ntm_dp * (N / 256), ncu = cu_count();
-        const int want = ndp > rp.tp.wgs ? ndp : rp.tp.wgs;
-        const dim3 grid(want < ncu ? want : ncu);
-        if (rp.rb == 3)
-          hipLaunchKernelGGL((gemm256s_kernel<T, Epi, true, 3>), grid, dim3(512), 0, s,
-                             (const T*)A, (const T*)W, M, N, K, epi, gm, rp.tp.ntm_dp, rp.tp.wgs,
-                             rp.tp.wide & 1);
-        else
-          hipLaunchKernelGGL((gemm256s_kernel<T, Epi, true, 2>), grid, dim3(512), 0, s,
-                             (const T*)A, (const T*)W, M, N, K, epi, gm, rp.tp.ntm_dp, rp.tp.wgs,
-                             rp.tp.wide & 1);
-        return hipGetLastError();
-      }
-      if (small_ok && variant == 0) variant = 259;   // 256-row tiles won: persistent kernel
-    }
+  const T* a = (const T*)A;
+  const T* w = (const T*)W;
+  const dim3 grid(p.grid), block(p.block);
+#define MICLIP_GEMM_LAUNCH(kernel, ...) \
+  hipLaunchKernelGGL(kernel, grid, block, 0, s, a, w, M, N, K, epi, ##__VA_ARGS__)
+  switch (p.kernel) {
+    case kGemmSplitK:
+      hipLaunchKernelGGL((gemm_nt_splitk_kernel<T>), dim3(p.grid, sk), block, 0, s, a, w, M, N, K,
+                         K / sk, skws);
+      hipLaunchKernelGGL((splitk_reduce_kernel<Epi>), dim3(p.reduce_grid), dim3(256), 0, s,
+                         (const float*)skws, sk, M, N, epi);
+      break;
+    case kGemmTile128:
+      MICLIP_GEMM_LAUNCH((gemm_nt_kernel<T, 128, 128, Epi>));
+      break;
+    case kGemmTile256S0:
+      MICLIP_GEMM_LAUNCH((gemm256_kernel<T, Epi, 0>), p.gm, p.ntm_dp, p.wide);
+      break;
+    case kGemmTile256S1:
+      MICLIP_GEMM_LAUNCH((gemm256_kernel<T, Epi, 1>), p.gm, p.ntm_dp, p.wide);
+      break;
+    case kGemmTile256S2:
+      MICLIP_GEMM_LAUNCH((gemm256_kernel<T, Epi, 2>), p.gm, p.ntm_dp, p.wide);
+      break;
+    case kGemmTile256S2Regs:
+      MICLIP_GEMM_LAUNCH((gemm256_kernel<T, Epi, 2, true>), p.gm, p.ntm_dp, p.wide);
+      break;
+    case kGemmPersist256P:
+      MICLIP_GEMM_LAUNCH((gemm256p_kernel<T, Epi>), p.gm);
+      break;
+    case kGemmRows256:
+      MICLIP_GEMM_LAUNCH((gemm256s_kernel<T, Epi>), p.gm, p.ntm_dp, p.wgs, p.wide);
+      break;
+    case kGemmRows256Staged:
+      if constexpr (TrAcc<Epi>::value)
+        MICLIP_GEMM_LAUNCH((gemm256s_kernel<T, Epi, false>), p.gm, p.ntm_dp, p.wgs, p.wide);
+      break;
+    case kGemmRows192:
+      if constexpr (TrAcc<Epi>::value && !IsPatch<Epi>::value)
+        MICLIP_GEMM_LAUNCH((gemm256s_kernel<T, Epi, true, 3>), p.gm, p.ntm_dp, p.wgs, p.wide);
+      break;
+    case kGemmRows128:
+      if constexpr (TrAcc<Epi>::value && !IsPatch<Epi>::value)
+        MICLIP_GEMM_LAUNCH((gemm256s_kernel<T, Epi, true, 2>), p.gm, p.ntm_dp, p.wgs, p.wide);
+      break;
   }
-  if (variant == 192 || variant == 129 || variant == 130)
-    return hipErrorInvalidValue;   // not a transposed-accumulator epilogue
-  if (variant == 259 && !IsPatch<Epi>::value && N % 256 == 0 && K >= 128) {
-    // persistent staggered kernel, LDS-staged epilogue + next-tile prefetch
-    const TailPlan tp = notail ? TailPlan{(M + 255) / 256, 0, 0} : plan_tail(M, N);
-    const int ndp = tp.ntm_dp * (N / 256), ncu = cu_count();
-    const int want = ndp > tp.wgs ? ndp : tp.wgs;
-    const int grid = want < ncu ? want : ncu;
-    if constexpr (TrAcc<Epi>::value) {
-      if (variant_tracc_off) {
-        hipLaunchKernelGGL((gemm256s_kernel<T, Epi, false>), dim3(grid), dim3(512), 0, s,
-                           (const T*)A, (const T*)W, M, N, K, epi, gm, tp.ntm_dp, tp.wgs,
-                           tp.wide & 1);
-        return hipGetLastError();
-      }
-    }
-    hipLaunchKernelGGL((gemm256s_kernel<T, Epi>), dim3(grid), dim3(512), 0, s, (const T*)A,
-                       (const T*)W, M, N, K, epi, gm, tp.ntm_dp, tp.wgs, tp.wide & 1);
-    return hipGetLastError();
-  }
-  if (variant == 3) {   // persistent 256x256
-    const int ncu = cu_count();
-    const int tiles = ((M + 255) / 256) * (N / 256);
-    // needs >= 2 K-tiles (the stream stages at most one tile ahead); the
-    // patch-embed epilogue keeps the one-tile-per-workgroup kernel
-    if (!IsPatch<Epi>::value && N % 256 == 0 && K >= 128) {
-      const int grid = tiles < ncu ? tiles : ncu;
-      hipLaunchKernelGGL((gemm256p_kernel<T, Epi>), dim3(grid), dim3(512), 0, s, (const T*)A,
-                         (const T*)W, M, N, K, epi, gm);
-      return hipGetLastError();
-    }
-  }
-
-  // Large problems: 256x256 tile (1 WG/CU, L2-friendly arithmetic intensity);
-  // small ones (text tower, tiny batches) keep more workgroups with 128x128.
-  const int tiles256 = ((M + 255) / 256) * (N / 256);
-  if (N % 256 == 0 && variant != 128 && (2 * tiles256 >= cu_count() || variant >= 256)) {
-    // default: the staggered schedule (SCHED 2) with the LDS-staged epilogue
-    // (full 512-B / 1-KiB row stores) for every epilogue; 260 = the register
-    // epilogue, 256 / 257 = SCHED 0 / 1. (The fp32 residual register epilogue
-    // was ~5 % faster with inline-asm x loads, but an asm load's destination
-    // is free for hipcc to reuse before the data lands: it faulted
-    // intermittently, so it is gone.)
-    if (variant == 0) variant = 258;
-    TailPlan tp = notail ? TailPlan{(M + 255) / 256, 0, 0} : plan_tail(M, N);
-    if (tp.wgs && tail_first) {
-      tp.wgs = (tp.wgs + 7) / 8 * 8;   // interleaved 8 per 16 blocks
-      tp.wide |= 2;
-    }
-    {
-      const int us = stagger ? 8 : 0;
-      const int tiles = tp.ntm_dp * (N / 256);
-      if (us > 0 && tiles >= 2 * cu_count()) tp.wide |= (us < 255 ? us : 255) << 8;
-    }
-    const dim3 grid(tp.ntm_dp * (N / 256) + tp.wgs);
-    if (variant == 260)
-      hipLaunchKernelGGL((gemm256_kernel<T, Epi, 2, true>), grid, dim3(512), 0, s, (const T*)A,
-                         (const T*)W, M, N, K, epi, gm, tp.ntm_dp, tp.wide);
-    else if (variant == 257)
-      hipLaunchKernelGGL((gemm256_kernel<T, Epi, 1>), grid, dim3(512), 0, s, (const T*)A,
-                         (const T*)W, M, N, K, epi, gm, tp.ntm_dp, tp.wide);
-    else if (variant == 256)
-      hipLaunchKernelGGL((gemm256_kernel<T, Epi, 0>), grid, dim3(512), 0, s, (const T*)A,
-                         (const T*)W, M, N, K, epi, gm, tp.ntm_dp, tp.wide);
-    else
-      hipLaunchKernelGGL((gemm256_kernel<T, Epi, 2>), grid, dim3(512), 0, s, (const T*)A,
-                         (const T*)W, M, N, K, epi, gm, tp.ntm_dp, tp.wide);
-    return hipGetLastError();
-  }
-  constexpr int BM = 128, BN = 128;
-  const int grid = ((M + BM - 1) / BM) * (N / BN);
-  hipLaunchKernelGGL((gemm_nt_kernel<T, BM, BN, Epi>), dim3(grid), dim3(256), 0, s,
-                     (const T*)A, (const T*)W, M, N, K, epi);
+#undef MICLIP_GEMM_LAUNCH
   return hipGetLastError();
 }
 

@@ -28,6 +28,7 @@
 #include "common.h"
 #include "epilogue.h"
 #include "kernels.h"
+#include "launch.h"
 #include "mx.h"
 
 #include <cstdlib>
@@ -950,17 +951,6 @@ __global__ __launch_bounds__(256) void quant_mx_h8_kernel(const _Float16* __rest
       }
     }
   }
-}
-
-int cu_count() {
-  static int ncu = [] {
-    int d = 0, n = 0;
-    if (hipGetDevice(&d) != hipSuccess ||
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d) != hipSuccess || n <= 0)
-      n = 256;
-    return n;
-  }();
-  return ncu;
 }
 
 // variant 0: the persistent kernel where it applies (K >= 256), else one tile per

@@ -23,6 +23,18 @@ auto dispatch_in_dtype(int dtype, F f) {
   return f(TypeTag<__bf16>{});
 }
 
+// Compute units of the current device, asked once; 256 (an MI355X) where the query fails
+inline int cu_count() {
+  static int ncu = [] {
+    int d = 0, n = 0;
+    if (hipGetDevice(&d) != hipSuccess ||
+        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d) != hipSuccess || n <= 0)
+      n = 256;
+    return n;
+  }();
+  return ncu;
+}
+
 // A kernel that may need more than 64 KiB of dynamic LDS opts in to the full 160 KiB
 inline hipError_t lds_opt_in(const void* fn, size_t lds) {
   if (lds <= 64 * 1024) return hipSuccess;

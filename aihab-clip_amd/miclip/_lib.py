@@ -42,7 +42,7 @@ EXPORTS = (
     "miclip_clock_probe",
     "miclip_model_destroy", "miclip_last_error", "miclip_abi_version",
     "miclip_model_bytes", "miclip_model_flags", "miclip_model_set_option", "miclip_set_gemm_variant", "miclip_set_profiling", "miclip_profile_read", "miclip_set_splits", "miclip_image_splits",
-    "miclip_op_gemm", "miclip_op_gemm_splitk", "miclip_op_ln_stats", "miclip_op_ln_fold", "miclip_op_gemm_ln",
+    "miclip_op_gemm", "miclip_gemm_plan", "miclip_op_gemm_splitk", "miclip_op_ln_stats", "miclip_op_ln_fold", "miclip_op_gemm_ln",
     "miclip_op_gemm_patch", "miclip_op_class_token", "miclip_op_layernorm_rows",
     "miclip_op_layernorm", "miclip_op_attention", "miclip_op_attention_q0", "miclip_op_im2col", "miclip_preprocess", "miclip_preprocess_aug",
     "miclip_row_norms", "miclip_class_centroids", "miclip_proto_scores",
@@ -145,6 +145,7 @@ def load_library(path: str = None):
         "miclip_image_splits": ([vp, i32], ctypes.c_int),
         "miclip_profile_read": ([vp, ctypes.POINTER(MiclipKernelStat), i32, i32], ctypes.c_int),
         "miclip_op_gemm": ([i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp], ctypes.c_int),
+        "miclip_gemm_plan": ([i32, i32, i32, i32, i32, i32, i32, ctypes.POINTER(i32)], ctypes.c_int),
         "miclip_op_layernorm": ([i32, vp, vp, vp, vp, i32, i32, i32, vp], ctypes.c_int),
         "miclip_op_layernorm_rows": ([i32, vp, vp, i32, vp, vp, vp, i32, i32, i32, vp],
                                      ctypes.c_int),

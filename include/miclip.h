@@ -769,6 +769,20 @@ int miclip_profile_read(miclip_model* m, miclip_kernel_stat* out, int32_t n, int
 int miclip_op_gemm(int32_t dtype, const void* A, const void* W, const float* bias, void* C,
                    int32_t M, int32_t N, int32_t K, int32_t epi, int32_t act, int32_t variant,
                    void* stream);
+/* The launch that miclip_op_gemm / _gemm_ln / _gemm_splitk / _gemm_patch would make for
+ * this shape, launching nothing (host only; no reference counterpart). epi: the codes
+ * above, 5 = the folded-LN store, 6 = the patch-embed epilogue; variant as there; sk <= 1:
+ * no split-K; ncu: the CU count to plan for, 0 = this device's (the only case that
+ * touches HIP). out = {kernel, grid, block, gm, ntm_dp, wgs, wide, 0}: workgroups,
+ * threads per workgroup and the kernel's tile-row group, tile-rows kept in tiles,
+ * row-tail tasks and tail flags (0 where the kernel takes none). kernel:
+ *   0 split-K pair (grid x sk workgroups, then the reduction)   1 gemm_nt_kernel 128x128
+ *   2 / 3 / 4 gemm256_kernel SCHED 0 / 1 / 2   5 gemm256_kernel SCHED 2, register epilogue
+ *   6 gemm256p_kernel   7 gemm256s_kernel, 256-row tiles   8 the same with the fp32
+ *   row-staging epilogue   9 / 10 gemm256s_kernel, 192- / 128-row tiles
+ * MICLIP_EINVAL where the launcher refuses (csrc/gemm_plan.h plan_gemm) or out is NULL. */
+int miclip_gemm_plan(int32_t M, int32_t N, int32_t K, int32_t epi, int32_t variant, int32_t sk,
+                     int32_t ncu, int32_t out[8]);
 
 /* Folded LayerNorm (ln_1 -> QKV, ln_2 -> c_fc of ResidualAttentionBlock,
  * clip/model.py:184-185): LN(x) . W^T + b computed as rs * (x . Wf^T - mean * colsum) + c

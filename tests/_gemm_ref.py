@@ -13,8 +13,8 @@ device its arguments live on.
   e_gelu / e_quick      the error the kernels' fp32 activation arithmetic is allowed
   interval_ok           out is the rounding of SOME value in [lo, hi] (RNE is monotone)
   fp16_grid             every fp16 pre-activation of the activation sweep
-  plan_tail / choose_rows / launch_choice
-                        the launcher's host-side plan as functions of (M, N, K, ncu)
+  plan_tail / choose_rows / launch_choice / launch_report
+                        the launcher's host-side plan as functions of (M, N, K, ncu, variant)
 
 T(x) for a float64 x means "x rounded to fp32, then RNE to T", the two steps an fp32
 epilogue performs; both are monotone, so T is.
@@ -30,6 +30,7 @@ FP32_MIN_NORMAL = 2.0 ** -126
 # gemm.hip: variant flags
 NO_TAIL = 1 << 16
 TAIL_FIRST = 1 << 17
+STAGGER = 1 << 18
 ROW_STAGING = 1 << 21
 
 
@@ -246,26 +247,89 @@ def shape_ok(M, N, K):
     return M >= 1 and N >= 128 and K >= 64 and N % 128 == 0 and K % 64 == 0
 
 
-def launch_choice(M, N, K, ncu, tracc=True, patch=False):
-    """launch() at variant 0: (kernel, plan). kernel is one of 'rows128', 'rows192'
-    (the persistent kernel's smaller tiles, transposed-accumulator epilogues only),
-    'persistent' (256-row tiles + tail), 'tile256' (one tile per workgroup + tail),
-    'tile128'. tracc: EpiStore / EpiStoreLN / the fp16 residual; patch: EpiPatch."""
+# miclip_gemm_plan's kernel codes (include/miclip.h), by position
+KERNELS = ("splitk", "tile128", "tile256_s0", "tile256_s1", "tile256", "tile256_regs",
+           "persistent_p", "persistent", "persistent_staged", "rows192", "rows128")
+CODES = (0, 3, 128, 129, 130, 192, 256, 257, 258, 259, 260)
+DEFAULT_GROUP = 4
+
+
+def launch_choice(M, N, K, ncu, tracc=True, patch=False, variant=0):
+    """launch(): (kernel, plan), or None where it refuses the variant. At variant 0 kernel is
+    one of 'rows128', 'rows192' (the persistent kernel's smaller tiles, transposed-accumulator
+    epilogues only), 'persistent' (256-row tiles + tail), 'tile256' (one tile per workgroup
+    + tail), 'tile128'. An explicit variant also reaches 'persistent_staged' (259 with
+    ROW_STAGING), 'persistent_p' (3) and 'tile256_s0' / '_s1' / '_regs' (256 / 257 / 260).
+    plan = the (ntm_dp, wgs, wide) the kernel receives, None where it takes none.
+    tracc: EpiStore / EpiStoreLN / the fp16 residual; patch: EpiPatch.
+    Restated from the launcher as it stood before csrc/gemm_plan.h: a chain of tests that
+    rewrite the code on the way, kept in that shape on purpose."""
     assert shape_ok(M, N, K)
+    no_tail, tail_first = bool(variant & NO_TAIL), bool(variant & TAIL_FIRST)
+    stagger, staging = bool(variant & STAGGER), bool(variant & ROW_STAGING)
+    code = (variant & ~(NO_TAIL | TAIL_FIRST | STAGGER | ROW_STAGING)) % 1000
+    if code not in CODES:
+        return None
     big = N % 256 == 0 and K >= 128
-    persistent = (not patch) and big and 2 * _cdiv(M, 256) * (N // 256) >= ncu
+    tiles256 = _cdiv(M, 256) * (N // 256)
+    whole = (_cdiv(M, 256), 0, 0)
+    by_size = code == 0
+    if by_size and not patch and big and 2 * tiles256 >= ncu:
+        code = 259
     if tracc and not patch:
-        small_ok = big and 2 * _cdiv(M, 128) * (N // 256) >= ncu
-        if (persistent or small_ok) and big:
-            rb, plan = choose_rows(M, N, ncu)
+        small_ok = by_size and big and 2 * _cdiv(M, 128) * (N // 256) >= ncu
+        if (code in (259, 192, 129, 130) or small_ok) and big and not staging:
+            rb, plan = 4, None
+            if code == 192:
+                rb, plan = 3, (_cdiv(M, 192), 0, 0)
+            elif code == 129:
+                rb, plan = 2, (_cdiv(M, 128), 0, 0)
+            elif code == 130:
+                rb, plan = 2, plan_tail(M, N, ncu, 128)
+            elif by_size:
+                rb, plan = choose_rows(M, N, ncu)
             if rb != 4:
                 return ("rows192" if rb == 3 else "rows128", plan)
-            persistent = True
-    if persistent:
-        return ("persistent", plan_tail(M, N, ncu))
-    if N % 256 == 0 and 2 * _cdiv(M, 256) * (N // 256) >= ncu:
-        return ("tile256", plan_tail(M, N, ncu))
+            if small_ok:
+                code = 259
+    if code in (192, 129, 130):
+        return None
+    if code == 259 and not patch and big:
+        plan = whole if no_tail else plan_tail(M, N, ncu)
+        return ("persistent_staged" if tracc and staging else "persistent", plan)
+    if code == 3 and not patch and big:
+        return ("persistent_p", None)
+    if N % 256 == 0 and code != 128 and (2 * tiles256 >= ncu or code >= 256):
+        ntm_dp, wgs, wide = whole if no_tail else plan_tail(M, N, ncu)
+        if wgs and tail_first:
+            wgs, wide = _cdiv(wgs, 8) * 8, wide | 2
+        if stagger and ntm_dp * (N // 256) >= 2 * ncu:
+            wide |= 8 << 8
+        name = {256: "tile256_s0", 257: "tile256_s1", 260: "tile256_regs"}.get(code, "tile256")
+        return (name, (ntm_dp, wgs, wide))
     return ("tile128", None)
+
+
+def launch_report(M, N, K, ncu, tracc=True, patch=False, variant=0, sk=1):
+    """What miclip_gemm_plan reports for this launch: (kernel code, grid, block, gm, ntm_dp,
+    wgs, wide), None where the launcher refuses. Split-K comes before the variant."""
+    if not shape_ok(M, N, K):
+        return None
+    if sk > 1:
+        return None if K % (sk * 64) else (0, _cdiv(M, 128) * (N // 128), 256, 0, 0, 0, 0)
+    choice = launch_choice(M, N, K, ncu, tracc, patch, variant)
+    if choice is None:
+        return None
+    name, plan = choice
+    code = variant & ~(NO_TAIL | TAIL_FIRST | STAGGER | ROW_STAGING)
+    gm = code // 1000 if code >= 1000 else DEFAULT_GROUP
+    if name == "tile128":
+        return (1, _cdiv(M, 128) * (N // 128), 256, 0, 0, 0, 0)
+    if name == "persistent_p":
+        return (6, min(_cdiv(M, 256) * (N // 256), ncu), 512, gm, 0, 0, 0)
+    tiles = plan[0] * (N // 256)
+    grid = tiles + plan[1] if name.startswith("tile256") else min(max(tiles, plan[1]), ncu)
+    return (KERNELS.index(name), grid, 512, gm) + plan
 
 
 def wide_tail_shape(ncu):

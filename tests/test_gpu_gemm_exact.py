@@ -21,7 +21,8 @@ C1  integer operands (A, W in [-3, 3], K <= 512, bias a multiple of 0.25 in [-40
     tiles with a non-transposed epilogue) are asserted refused.
     Cases: 128x128 12, one-tile 256x256 72, persistent 72, multi-tile walk 3, row tails
     30 narrow + 5 wide, 192- / 128-row tiles 32 -- 226, each in both groups: 452 -- and
-    patch 6, refusals 1: 459.
+    patch 6, refusals 1: 459. One more case launches nothing: the launcher's own plan
+    (miclip_gemm_plan) for the row-tail shapes equals the restated one.
 C2  float operands (outlier channels up to 2^10, an all-zero row in A and in W): fp32
     outputs |C - ref64| <= bar S, S = |A||W|^T + |b| (+ |x0| for the residual), bar =
     min(4 x measured, (K + 8) 2^-23); 16-bit outputs interval_ok(ref64 -+ bar S), through
@@ -381,6 +382,33 @@ def test_exact_row_tail_wide(lib, variant, group):
     assert plan[2] == 1 and plan[1] > 0
     print(f"M {M} N {N} plan {plan}")
     _run_forms(lib, M, N, 128, variant, True, group)
+
+
+def test_row_tail_shapes_reach_the_tail_kernels(lib):
+    """The premise of the two tests above, checked instead of assumed: at this device's CU
+    count the launcher's own plan (miclip_gemm_plan, ncu = 0) equals the restated one for
+    every shape and variant they build, and it runs row-tail tasks of the kind they name.
+    No kernel runs."""
+    ncu, K = _ncu(), 128
+    shapes = [(v, (128 if v == 130 else 256) * _step(1024) + r, 1024, 0)
+              for v in (258, 260, 258 | TF, 259, 0, 130) for r in (1, 16, 17, 37, 256)]
+    wide = G.wide_tail_shape(ncu)
+    if wide is not None:
+        shapes += [(v, wide[0], wide[1], 1) for v in (258, 260, 258 | TF, 259, 0)]
+    kernels = set()
+    for variant, M, N, wide_bit in shapes:
+        for epi, tracc in ((0, True), (2, False)):
+            out = (ctypes.c_int32 * 8)()
+            rc = lib.miclip_gemm_plan(M, N, K, epi, variant, 1, 0, out)
+            want = G.launch_report(M, N, K, ncu, tracc, False, variant)
+            print(f"variant {variant:#x} M {M} N {N} epi {epi}: rc {rc} plan {list(out)[:7]}")
+            if variant == 130 and not tracc:
+                assert rc == EINVAL and want is None
+                continue
+            assert rc == 0 and tuple(out[:7]) == want
+            assert out[5] > 0 and out[6] & 1 == wide_bit, "no row tail of the expected kind"
+            kernels.add(G.KERNELS[out[0]])
+    assert kernels == {"tile256", "tile256_regs", "persistent", "rows128"}
 
 
 @pytest.mark.parametrize("K", [128, 192])
